@@ -12,7 +12,10 @@ set_timesteps(50), one 1x1x128^3 volume per GPU per step.  A "step" = one comple
 the network is not the zero function), synthetic Gaussian noise input.  Volumes are independent chains: ranks share nothing
 on the data path (weak scaling, no collective); the barrier / all-reduce below only brackets the timing.
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields.  A plain run sets up, warms up, times the --steps chains, writes
+rank 0's final sample of the last timed chain with --dump-outputs DIR (DIR/sample.npy, float32: same arguments, same inputs, so two
+builds can be compared output for output) and prints the line.  --full also samples package power over the timed steps and adds
+  "output_finite", "unet_forward_ms", "kernel_breakdown_ms", "package_power_w", "joules_per_volume";
   "roofline":     the dominant kernel (implicit-GEMM convolution) -- algorithmic FLOPs per launch / HIP-event time per launch
                   over one instrumented forward, against the dense bf16 MFMA peak;
   "cpu_baseline": kind "port" = oracle/restatement.py (the reference algorithm restated on torch-CPU fp32, pinned to outputs of the unmodified
@@ -239,8 +242,13 @@ def main() -> None:
     ap.add_argument("--inference-steps", type=int, default=50)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--graph", type=int, default=0, help="replay the UNet forward from a HIP graph (measured slower than eager launches on ROCm 7.2 at this size: 18.7-19.5 vs 14.5-14.8 ms per iteration, round 3)")
-    ap.add_argument("--cpu-baseline", default="full", choices=["full", "small", "off"])
+    ap.add_argument("--cpu-baseline", default="full", choices=["full", "small", "off"], help="the CPU leg of a --full run")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: package power, "
+                                                        "the instrumented forward (roofline, kernel breakdown), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed chain's final sample (rank 0) as DIR/sample.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if needs_self_launch(args.gpus, os.environ):  # `python bench.py --gpus N` as the driver calls it: become N ranks under torch.distributed.run
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -286,7 +294,7 @@ def main() -> None:
     for _ in range(args.warmup):
         out = inferer.sample(noise, model, sched, verbose=False)
     sync()
-    power = PowerSampler(local_rank) if rank == 0 else None
+    power = PowerSampler(local_rank) if rank == 0 and args.full else None
     if power is not None:
         power.start()
     t0 = time.perf_counter()
@@ -299,14 +307,18 @@ def main() -> None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    finite = bool(torch.isfinite(out.float()).all().item())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "sample.npy"), out.float().cpu().numpy())
 
     # ---- per-kernel roofline: one instrumented eager forward (HIP events on the launch stream around every launch) ---------
     roof = None
     fwd_ms = None
     eps_gpu = None
     breakdown = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         tt = torch.tensor([500.0], device=dev)
         eps_gpu = model(noise, tt).float().cpu()  # warm; kept: compared with the CPU oracle's forward of the same input below
         torch.cuda.synchronize()
@@ -354,7 +366,7 @@ def main() -> None:
     # round 1), (2) with the best count: DDIM steps (UNet forward + scheduler step) at full size at t = 980, 500, 20 -- median;
     # (3) the t = 500 prediction is compared with the GPU forward of the same noise volume.
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline != "off":
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import restatement as R  # test infrastructure: the CPU statement of the reference algorithm (checker / baseline only; never on the product path)
 
@@ -422,20 +434,23 @@ def main() -> None:
                        "parallelism": f"{world} independent replicas (batch-sharded, no data-path collective)", "hip_graph": bool(args.graph),
                        "process_group": None if dist is None else f"nccl (RCCL), world_size {world}",
                        "self_launched": os.environ.get("GM_BENCH_SELF_LAUNCHED") == "1"},
-            "unet_forward_ms": None if fwd_ms is None else round(fwd_ms, 3),
             "ms_per_ddim_iteration": round(1e3 * elapsed / args.steps / args.inference_steps, 3),
-            "output_finite": finite,
-            "roofline": roof, "package_power_w": power_stats,
-            "joules_per_volume": None if not power_stats else round(power_stats["mean_w"] * elapsed / args.steps, 1),  # what bounds this loop: it runs at the power cap
-            "cpu_baseline": cpu,
-            "speedup_vs_cpu": None if cpu is None else round(vol_s / cpu["value"], 1),
-            # per kernel label: algorithmic FLOP and HBM rates of one forward; frac_mfma / frac_hbm = those rates over the nominal peaks (the larger one names the bound)
-            "kernel_breakdown_ms": {k: dict(launches=v["launches"], ms=round(v["ms"], 3),
-                                            tflops=round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2), gbs=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1),
-                                            frac_mfma=round(v["flops"] / max(v["ms"], 1e-9) / 1e9 / (MFMA_BF16_PEAK_TFLOPS if dtype == torch.bfloat16 else 157.3), 3),
-                                            frac_hbm=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS, 3))
-                                    for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"])},
         }
+        if args.full:
+            line.update({
+                "unet_forward_ms": None if fwd_ms is None else round(fwd_ms, 3),
+                "output_finite": bool(torch.isfinite(out.float()).all().item()),
+                "roofline": roof, "package_power_w": power_stats,
+                "joules_per_volume": None if not power_stats else round(power_stats["mean_w"] * elapsed / args.steps, 1),  # what bounds this loop: it runs at the power cap
+                "cpu_baseline": cpu,
+                "speedup_vs_cpu": None if cpu is None else round(vol_s / cpu["value"], 1),
+                # per kernel label: algorithmic FLOP and HBM rates of one forward; frac_mfma / frac_hbm = those rates over the nominal peaks (the larger one names the bound)
+                "kernel_breakdown_ms": {k: dict(launches=v["launches"], ms=round(v["ms"], 3),
+                                                tflops=round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2), gbs=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1),
+                                                frac_mfma=round(v["flops"] / max(v["ms"], 1e-9) / 1e9 / (MFMA_BF16_PEAK_TFLOPS if dtype == torch.bfloat16 else 157.3), 3),
+                                                frac_hbm=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS, 3))
+                                        for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"])},
+            })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

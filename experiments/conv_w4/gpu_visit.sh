@@ -11,7 +11,7 @@ step convab; BENCH_PLAIN=1 timeout 300 python tools/bench_conv.py 14,22,23 > $OU
 step convab-again; BENCH_PLAIN=1 timeout 300 python tools/bench_conv.py 23,14,23,14 > $OUT/r5v4_convab2.txt 2>&1; cat $OUT/r5v4_convab2.txt >> $L
 bq() {
   TAGN=${1//[^A-Za-z0-9]/_}
-  env $1 timeout 300 python bench.py --steps 3 --warmup 1 --cpu-baseline off 2> $OUT/r5v4_benchq_$TAGN.err | tail -1 > $OUT/r5v4_benchq_$TAGN.json
+  env $1 timeout 300 python bench.py --full --steps 3 --warmup 1 --cpu-baseline off 2> $OUT/r5v4_benchq_$TAGN.err | tail -1 > $OUT/r5v4_benchq_$TAGN.json
   python - $OUT/r5v4_benchq_$TAGN.json "$1" >> $L <<'PY'
 import json, sys
 try:

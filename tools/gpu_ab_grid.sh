@@ -6,7 +6,7 @@ if [[ "${1:-}" == *t* ]]; then
 fi
 for G in 0 -1; do
   echo "== grid policy $G"
-  GM_CONV_DMA_GRID=$G timeout 300 python bench.py --steps 3 --warmup 1 --cpu-baseline off 2>/dev/null | tail -1 | python -c "
+  GM_CONV_DMA_GRID=$G timeout 300 python bench.py --full --steps 3 --warmup 1 --cpu-baseline off 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print(d['value'], d['ms_per_ddim_iteration'], d['unet_forward_ms'], d['roofline']['achieved'], d['roofline']['frac'], d['roofline']['avg_launch_ms'])"

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU visit that produces the records of a finished tree: the PMC traffic passes that stamp profiles/pmc_hbm_traffic_current.json, the default bench (CPU leg on),
+# One GPU visit that produces the records of a finished tree: the PMC traffic passes that stamp profiles/pmc_hbm_traffic_current.json, the full bench (CPU leg on),
 # rocprofv3 --kernel-trace --stats of the bench, per-launch layer times (C2, C3 latent UNet, 256^3 autoencoder), the other configurations' benches, the GPU suite.
 #   usage: GM_GIT_HEAD=$(git rev-parse --short HEAD) tools/gpu_final_records.sh TAG [notests]
 set -u
@@ -10,7 +10,7 @@ step() { echo "== $1 ($(date +%T))" >> $L; }
 step pmc; timeout 900 bash tools/pmc_traffic.sh >> $L 2>&1; cp $OUT/pmc_traffic/summary.json $OUT/${TAG}_pmc_traffic.json 2>/dev/null; cp $OUT/pmc_traffic/summary.json profiles/pmc_hbm_traffic_current.json 2>/dev/null
 # (the eager C4 step issues ~620 launches from Python and follows the host's clock: it runs BEFORE the 128-thread CPU-baseline leg of the bench, behind which it read 44-48 ms instead of 41)
 step train; timeout 600 python tools/bench_train.py > $OUT/${TAG}_train.json 2> /dev/null; grep '^{' $OUT/${TAG}_train.json | head -c 900 >> $L; echo >> $L
-step bench; timeout 900 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $L; grep '^{' $OUT/${TAG}_bench.json | head -c 4500 >> $L; echo >> $L
+step bench; timeout 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $L; grep '^{' $OUT/${TAG}_bench.json | head -c 4500 >> $L; echo >> $L
 step prof
 rm -rf $OUT/${TAG}_prof
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/${TAG}_prof -o p -- python $OLDPWD/bench.py --steps 1 --warmup 1 --cpu-baseline off > $OLDPWD/$OUT/${TAG}_prof.log 2>&1)

@@ -23,9 +23,9 @@ if [[ $STAGES == *s* ]]; then
   echo "smoke rc=$?" >> $OUT/round.log; tail -2 $OUT/smoke.log >> $OUT/round.log
 fi
 if [[ $STAGES == *b* ]]; then
-  timeout 300 python bench.py --size 32 --steps 1 --warmup 1 --inference-steps 4 --cpu-baseline small --graph 0 > $OUT/bench_small.log 2>&1
+  timeout 300 python bench.py --full --size 32 --steps 1 --warmup 1 --inference-steps 4 --cpu-baseline small --graph 0 > $OUT/bench_small.log 2>&1
   echo "bench_small rc=$?" >> $OUT/round.log; tail -c 1500 $OUT/bench_small.log >> $OUT/round.log
-  timeout 1200 python bench.py --steps 2 --warmup 1 > $OUT/bench.log 2>&1
+  timeout 1200 python bench.py --full --steps 2 --warmup 1 > $OUT/bench.log 2>&1
   echo "bench rc=$?" >> $OUT/round.log; tail -c 3000 $OUT/bench.log >> $OUT/round.log
 fi
 if [[ $STAGES == *l* ]]; then

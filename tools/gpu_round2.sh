@@ -57,11 +57,11 @@ PY
   done
 fi
 if [[ $STAGES == *b* ]]; then
-  timeout 1500 python bench.py ${BENCH_ARGS:---steps 3 --warmup 1} > $OUT/r2_bench.log 2>&1
+  timeout 1500 python bench.py --full ${BENCH_ARGS:---steps 3 --warmup 1} > $OUT/r2_bench.log 2>&1
   echo "bench rc=$?" >> $LOG; tail -c 6000 $OUT/r2_bench.log >> $LOG
 fi
 if [[ $STAGES == *a* ]]; then  # A/B: the same bench with the two-pass GroupNorm-apply (no in-LDS prologue)
-  GM_DMA_FUSED_PROLOGUE=0 timeout 900 python bench.py --steps 2 --warmup 1 --cpu-baseline off > $OUT/r2_bench_twopass.log 2>&1
+  GM_DMA_FUSED_PROLOGUE=0 timeout 900 python bench.py --full --steps 2 --warmup 1 --cpu-baseline off > $OUT/r2_bench_twopass.log 2>&1
   echo "bench_twopass rc=$?" >> $LOG; tail -c 2500 $OUT/r2_bench_twopass.log >> $LOG
 fi
 if [[ $STAGES == *x* ]]; then  # A/B of conv debug flags (timing only)

@@ -2,7 +2,7 @@
 # One parameterised GPU visit (replaces the per-visit scripts of round 3): tools/gpu_visit.sh TAG STEP [STEP ...]
 # Every step appends to gpurun_out/TAG_*.  Steps:
 #   tests[:EXPR]    pytest -m gpu (optionally -k EXPR)            smoke       __graft_entry__.smoke()
-#   bench           python bench.py (default run, CPU leg on)     benchq      bench.py --steps 3 --warmup 1 --cpu-baseline off
+#   bench           python bench.py --full (CPU leg on)           benchq      bench.py --full --steps 3 --warmup 1 --cpu-baseline off
 #   convab:CFGS     tools/bench_conv.py CFGS with BENCH_PLAIN=1   layers      tools/layer_times.py
 #   ab:ENV=VAL      tools/ab_lib.py under that environment        c3 c5 c1b train   the other BASELINE configurations' benches
 #   prof            rocprofv3 --kernel-trace --stats of the bench pmc  tools/pmc_traffic.sh
@@ -25,8 +25,8 @@ for STEP in "$@"; do
       grep -n "^_____.* test_\|^E  \|passed\|failed" $OUT/${TAG}_tests.log | head -40 >> $LOG
       grep "\[parity\]" $OUT/${TAG}_tests.log > $OUT/${TAG}_parity.txt ;;
     smoke) timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/${TAG}_smoke.log 2>&1; tail -2 $OUT/${TAG}_smoke.log >> $LOG ;;
-    bench) timeout 900 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $LOG; grep '^{' $OUT/${TAG}_bench.json >> $LOG ;;
-    benchq) env $ARG timeout 300 python bench.py --steps 3 --warmup 1 --cpu-baseline off 2> $OUT/${TAG}_benchq.err | tail -1 > $OUT/${TAG}_benchq_${ARG//[^A-Za-z0-9]/_}.json
+    bench) timeout 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $LOG; grep '^{' $OUT/${TAG}_bench.json >> $LOG ;;
+    benchq) env $ARG timeout 300 python bench.py --full --steps 3 --warmup 1 --cpu-baseline off 2> $OUT/${TAG}_benchq.err | tail -1 > $OUT/${TAG}_benchq_${ARG//[^A-Za-z0-9]/_}.json
       python - "$OUT/${TAG}_benchq_${ARG//[^A-Za-z0-9]/_}.json" "$ARG" >> $LOG <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
