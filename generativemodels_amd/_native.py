@@ -132,6 +132,7 @@ PROTOTYPES = {
                                       c_vp]),
     "gm_pack_subpixel_weight": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_attention_max_head_dim": (C.c_int, []),
+    "gm_attention_max_wide_head_dim": (C.c_int, []),
     "gm_linear_rows": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_linear_rows_affine_vt": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, C.c_int, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, C.c_int,
                                            C.c_int, C.c_int, c_vp]),

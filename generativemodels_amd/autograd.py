@@ -9,9 +9,10 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
   group_norm_act  forward: per-channel statistics -> (scale, shift) -> one apply pass (+ SiLU)
                   backward: gm_gn_bwd_stats / _finalize / _apply (dx, dgamma, dbeta)
   upsample_conv   nearest 2x folded into the convolution; backward: dgrad on the fine grid, 2x sum-pool; dW against the upsampled input
-  attention       forward: the flash-attention kernel; backward: the fused flash backward gm_attention_backward (head dims 16 .. 256: scores
-                  recomputed per tile, nothing L x L stored); other head dims per (sample, head) in fp32 -- scores, softmax, dV = P^T dO,
-                  dP = dO V^T, dS (gm_softmax_bwd), dQ = dS K, dK = dS^T Q -- on the GEMM / weight-gradient kernels (up to 8192 tokens)
+  attention       forward: the flash-attention kernel (head dims up to 256; 257 .. 1024 on the sliced wide-head kernel); backward: the fused
+                  flash backward gm_attention_backward (head dims 16 .. 256: scores recomputed per tile, nothing L x L stored); other head dims
+                  (and every head dim above 256, unpadded) per (sample, head) in fp32 -- scores, softmax, dV = P^T dO, dP = dO V^T,
+                  dS (gm_softmax_bwd), dQ = dS K, dK = dS^T Q -- on the GEMM / weight-gradient kernels (up to 8192 tokens)
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -441,7 +442,9 @@ class _Attention(torch.autograd.Function):
                 return (*grads, None, None)
         if dh in ops.ATTENTION_BWD_HEAD_DIMS:
             return (*_attention_backward(q, k, v, o, go, heads, scale), None, None)
-        # any other head dim (<= 256: the forward's bound): zero-pad every head to the next width the kernels are built for.  Zero channels add
+        if dh > ops.lib().gm_attention_max_head_dim():
+            return (*_attention_backward_wide(q, k, v, go, heads, scale), None, None)
+        # any other head dim (<= 256): zero-pad every head to the next width the kernels are built for.  Zero channels add
         # nothing to q k^T, and v's zero channels give o / dO zero channels: the products are unchanged, the padded gradient channels are dropped.
         dhp = min(d for d in ops.ATTENTION_BWD_HEAD_DIMS if d >= dh)
 
@@ -480,6 +483,25 @@ def _attention_backward(q, k, v, o, go, heads, scale):
     # 2.5 ms); the composed path materialises fp32 L x L matrices, so long sequences always take the fused flash kernels
     if long_seq or not (b * heads <= 2 and max(lq, lk) >= 2048):
         return ops.attention_backward(q, k, v, o, go, heads, scale)  # fused flash backward: scores recomputed tile by tile, any sequence length
+    return _attention_backward_composed(q, k, v, go, heads, scale)
+
+
+def _attention_backward_wide(q, k, v, go, heads, scale):
+    """(dq, dk, dv) for head dims above the fused backward kernels' 256 (the forward's sliced wide-head kernel): the composed per-(sample, head)
+    fp32 path, unpadded -- its GEMM / weight-gradient / softmax kernels take any head dim -- up to ATTENTION_BWD_MAX_TOKENS per side (it
+    materialises the fp32 Lq x Lk score matrices)."""
+    lq, lk = q.shape[1], k.shape[1]
+    if max(lq, lk) > ATTENTION_BWD_MAX_TOKENS:
+        raise ValueError(f"attention backward with head dim {q.shape[2] // heads} (> {ops.lib().gm_attention_max_head_dim()}) is limited to "
+                         f"{ATTENTION_BWD_MAX_TOKENS} tokens per side (got {lq} queries x {lk} keys)")
+    return _attention_backward_composed(q, k, v, go, heads, scale)
+
+
+def _attention_backward_composed(q, k, v, go, heads, scale):
+    """Per (sample, head) in fp32: S = Q K^T, P = softmax(scale S), dV = P^T dO, dP = dO V^T, dS, dQ = dS K, dK = dS^T Q."""
+    b, lq, c = q.shape
+    lk = k.shape[1]
+    dh = c // heads
     f32 = torch.float32
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
 

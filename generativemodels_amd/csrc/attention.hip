@@ -358,7 +358,7 @@ static int dispatch_attn(const GmAttnDesc& d, hipStream_t st) {
   return -1;
 }
 
-extern "C" int gm_attention_max_head_dim(void) { return 256; }
+extern "C" int gm_attention_max_head_dim(void) { return GM_ATTN_MAX_DH; }
 extern "C" int gm_attention_dma_try(const GmAttnDesc* dp, void* stream);     // attention_dma.hip
 extern "C" int gm_attention_decode_try(const GmAttnDesc* dp, void* stream);  // small_ops.hip
 
@@ -368,7 +368,7 @@ extern "C" int gm_attention_forward(const GmAttnDesc* dp, void* stream) {
   GM_REQUIRE(d.q && d.k && d.v && d.o, "null tensor pointer");
   GM_REQUIRE(d.B >= 0 && d.H > 0 && d.dh > 0, "bad batch / head geometry");
   GM_REQUIRE(d.Lk > 0, "attention needs at least one key");
-  GM_REQUIRE(d.dh <= 256, "head dim > 256 is not supported by the gfx950 attention kernel");
+  GM_REQUIRE(d.dh <= GM_ATTN_WIDE_MAX_DH, "head dim > 1024 is not supported by the gfx950 attention kernels");
   GM_REQUIRE((long long)d.B * d.H <= 65535, "too many (batch, head) pairs for one launch");
   if (d.B == 0 || d.Lq == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -378,7 +378,8 @@ extern "C" int gm_attention_forward(const GmAttnDesc* dp, void* stream) {
   GM_REQUIRE(d.lse == nullptr, "GmAttnDesc.lse is written by the LDS-DMA path only (a workspace of gm_attention_workspace_bytes() > 0 bytes)");
   GM_REQUIRE(!d.vt_packed, "GmAttnDesc.vt_packed needs the LDS-DMA path (a workspace of gm_attention_workspace_bytes() bytes)");
   int rc;
-  if (d.dtype == GM_F32) rc = dispatch_attn<float>(d, st);
+  if (d.dh > GM_ATTN_MAX_DH) rc = gm_attn_wide_dispatch(d, st);  // wide heads: output slices of 256 channels (attention_wide.hip)
+  else if (d.dtype == GM_F32) rc = dispatch_attn<float>(d, st);
   else if (d.dtype == GM_BF16) rc = dispatch_attn<bf16_raw>(d, st);
   else GM_FAIL(-2, "unsupported dtype");
   GM_REQUIRE(rc == 0, "dispatch failed");

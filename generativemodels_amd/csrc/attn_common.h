@@ -4,6 +4,9 @@
 
 // key ranges of the split-KV single-query attention of the decode step (small_ops.hip; the merge code unrolls over it)
 #define GM_DECODE_KV_SPLITS 16
+// widest head the register-staged kernels serve in one pass (attention.hip), and the widest the sliced kernel serves (attention_wide.hip)
+#define GM_ATTN_MAX_DH 256
+#define GM_ATTN_WIDE_MAX_DH 1024
 
 struct GmAttnDesc {
   const void* q; long long q_ld;
@@ -41,6 +44,8 @@ struct GmAttnBwdDesc {
 };
 
 #ifdef __HIPCC__
+// 256 < dh <= GM_ATTN_WIDE_MAX_DH, fp32 / bf16, after gm_attention_forward's descriptor checks (attention_wide.hip); 0 = launched
+int gm_attn_wide_dispatch(const GmAttnDesc& d, hipStream_t st);
 // The four lanes l15 + 16 * {0, 1, 2, 3} of a wave hold partial results of one MFMA column: max / sum over them by gfx950's lane-swap VALU
 // instructions (v_permlane32_swap exchanges the wave's halves, v_permlane16_swap the odd and even 16-lane rows) instead of two ds_bpermute
 // round trips through the LDS pipeline.  Every lane receives the same value, operands combined in a fixed order.

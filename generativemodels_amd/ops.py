@@ -1617,6 +1617,11 @@ def bias_grad(gy: torch.Tensor, per_sample: bool = False) -> torch.Tensor:
     # Fresh statistics, never the tensor's cached table: a gradient tensor can be accumulated IN PLACE by the autograd engine after a first
     # consumer attached its column sums to the Python object (dres = gy hands the same object to two branches) -- measured as 12-24 %
     # errors in exactly the bias gradients behind an identity residual.
+    v = rows_of(gy) // max(n, 1)
+    if n > 0 and v > 0 and lib().gm_gn_channel_stats_slots(gy.data_ptr(), arena_ld(gy), v, c, dt_code(gy.dtype)) <= 0:
+        # wider than one statistics launch covers (the 4096-channel GEGLU projection of a 512-wide transformer block): 256-channel slices, each
+        # served by the kernel whatever its alignment
+        return torch.cat([bias_grad(gy[..., c0:c0 + 256], per_sample) for c0 in range(0, c, 256)], dim=-1)
     st = _fresh_channel_stats(gy)
     out = torch.empty((n, c) if per_sample else (c,), dtype=torch.float32, device=gy.device)
     check(lib().gm_stats_colsum(st.data_ptr(), st.shape[0], n, c, out.data_ptr(), int(per_sample), _stream()), "gm_stats_colsum")
@@ -1944,8 +1949,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
     if c % heads != 0 or k.shape[2] != c or v.shape[2] != c or v.shape[1] != lk:
         raise ValueError("attention operand shapes are inconsistent")
     dh = c // heads
-    if dh > lib().gm_attention_max_head_dim():
-        raise ValueError(f"head dim {dh} exceeds the gfx950 attention kernel limit ({lib().gm_attention_max_head_dim()})")
+    if dh > lib().gm_attention_max_wide_head_dim():  # (above gm_attention_max_head_dim() = 256: the sliced wide-head kernel, attention_wide.hip)
+        raise ValueError(f"head dim {dh} exceeds the gfx950 attention kernel limit ({lib().gm_attention_max_wide_head_dim()})")
     if out is None:
         out = torch.empty((b, lq, c), dtype=q.dtype, device=q.device)
     d = GmAttnDesc()

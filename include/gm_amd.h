@@ -276,7 +276,11 @@ typedef struct GmAttnDesc {
   float* lse;                 /* optional fp32 [B*H][Lq]: log sum_k exp(scale q.k) per query, written by the LDS-DMA path only (must be NULL otherwise);
                                * the training forward keeps it for gm_attention_backward_fused */
 } GmAttnDesc;
+/* widest head served by the single-pass kernels (register-staged / LDS-DMA; 256) */
 int gm_attention_max_head_dim(void);
+/* widest head gm_attention_forward serves at all (1024): 256 < dh <= this runs the sliced wide-head kernel -- 64 queries x 256 output channels per
+ * work-group, the scores recomputed per slice over the whole head dim (fp32 / bf16; stats, lse and vt_packed must stay NULL / 0 there) */
+int gm_attention_max_wide_head_dim(void);
 /* bytes of scratch the fastest kernel for this geometry wants (0: none; the descriptor's workspace fields are not read) */
 long long gm_attention_workspace_bytes(const GmAttnDesc* d);
 /* partials S the launch writes into GmAttnDesc.stats; 0 = this geometry does not fuse the output statistics (the split-KV form of the LDS-DMA
@@ -285,6 +289,8 @@ long long gm_attention_stats_slots(const GmAttnDesc* d);
 /* Tests / benchmarks only: pin the LDS-DMA kernel variant -- queries per wave = 16 * qf (qf 1 or 2) and the number of key slices of the
  * split-KV form (1..8) -- instead of the size-based choice; 0 restores the automatic choice for that knob.  Process-wide. */
 void gm_attention_dma_set_variant(int qf, int nsplit);
+/* O = softmax(scale Q K^T) V (+ res) for head dims 1 .. gm_attention_max_wide_head_dim(): dh <= 256 on the single-pass kernels, 256 < dh <= 1024 on the
+ * sliced wide-head kernel (every GmAttnDesc field but stats / lse / vt_packed; deterministic, no allocation: capturable in a HIP graph) */
 int gm_attention_forward(const GmAttnDesc* d, void* stream);
 
 /* ---- autoregressive transformer helpers (networks/nets/transformer.py, inferers/inferer.py:1126-1330) ------------------------ */
