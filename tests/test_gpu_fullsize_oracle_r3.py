@@ -325,7 +325,8 @@ def test_c4_latent_unet_parameter_gradients_at_real_dims_match_the_oracle_autogr
 def test_c5_decode_step_over_a_long_prefix_matches_the_oracle_forward(name, cfg, batch, ntok):
     """Every position's step logits against the oracle's full causal forward of the same tokens (transformer.py:98-106): past 64 keys more than
     one key range of the split-KV attention is live, past 1024 every one of the 16; the step with a device-side position (the form a HIP graph
-    replays) must give the same bits as the step with a host position."""
+    replays) must give the same bits as the step with a host position.  The model's own full-sequence forward of the same tokens (the causal register-staged
+    attention kernel at 1100 tokens x 8 heads of 32, and at 700 tokens x 3 heads of 24 in batch 2) is held to the same oracle output under the same bars."""
     from generativemodels_amd.networks.nets import DecoderOnlyTransformer
 
     tr = DecoderOnlyTransformer(**cfg).eval()
@@ -344,6 +345,11 @@ def test_c5_decode_step_over_a_long_prefix_matches_the_oracle_forward(name, cfg,
         bar = _fp32_bar if dtype == torch.float32 else _bf16_bar
         for lo, hi in ((0, 64), (64, 256), (256, ntok)):
             bar(got[:, lo:hi], want[:, lo:hi], f"{name}: step logits at positions {lo}..{hi - 1} ({str(dtype)[6:]})")
+        # the model's own full-sequence forward: the causal register-staged attention kernel at ntok tokens inside the network (several query blocks and key
+        # tiles, two or four wave groups), where the steps above run the single-query decode kernel
+        full = m(td)
+        for lo, hi in ((0, 64), (64, 256), (256, ntok)):
+            bar(full[:, lo:hi], want[:, lo:hi], f"{name}: full causal forward logits at positions {lo}..{hi - 1} ({str(dtype)[6:]})")
         pos_dev = torch.zeros(1, dtype=torch.int32, device=DEV)
         lg = torch.empty((batch, cfg["num_tokens"]), dtype=dtype, device=DEV)
         for p in (0, 63, 64, 300, ntok - 1):  # rewrites cache row p with the values it already holds
