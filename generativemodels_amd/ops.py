@@ -11,6 +11,7 @@ import math
 import os
 import threading
 import weakref
+from collections import namedtuple
 from typing import Optional, Sequence
 
 import torch
@@ -648,9 +649,9 @@ def _fresh_channel_stats(x: torch.Tensor) -> torch.Tensor:
 
 
 GN_IN_CONSUMER = os.environ.get("GM_GN_IN_CONSUMER", "1") != "0"  # short statistic tables: the fold + finalisation in the consumer convolution's prologue (cfg 24 / 25)
-GN_IN_TOKEN_GEMM = os.environ.get("GM_GN_IN_TOKEN_GEMM", "1") != "0"    # ... and in the wide token GEMM (the q | k | v projection of an attention block)
-GN_IN_SPLIT_SLICES = os.environ.get("GM_GN_IN_SPLIT_SLICES", "1") != "0"  # ... also in the K slices of a split launch (conv_sk.hip, second half of round 6)
-GN_IN_CONSUMER_MAX_ROWS = int(os.environ.get("GM_GN_IN_CONSUMER_MAX_ROWS", "128"))  # = GN_SHORT_MAX_ROWS of csrc/gm_common.h (64 until the 32^3 level's 128-row tables were measured)
+GN_IN_TOKEN_GEMM = True  # ... and in the wide token GEMM (the q | k | v projection of an attention block)
+GN_IN_SPLIT_SLICES = True  # ... also in the K slices of a split launch (conv_sk.hip, second half of round 6)
+GN_IN_CONSUMER_MAX_ROWS = 128  # = GN_SHORT_MAX_ROWS of csrc/gm_common.h (64 until the 32^3 level's 128-row tables were measured)
 
 
 class GnRecipe:
@@ -727,7 +728,7 @@ SPLITK_MAX_TILES = 256   # split when the unsplit launch has fewer work-groups t
 # ... into as many slices as it takes to reach about this many.  One per CU: a slice work-group of conv_sk.hip owns its CU's LDS, so a second wave of
 # work-groups runs after the first (round 3, two per CU on the general tile kernel: 512; measured on the C3 latent UNet: 1.657 vs 1.678 ms per forward)
 SPLITK_TARGET_WGS = int(os.environ.get("GM_CONV_SPLITK_WGS", "256"))
-SPLITK_MAX = int(os.environ.get("GM_CONV_SPLITK_MAX", "8"))
+SPLITK_MAX = 8
 _SK_KERNEL = os.environ.get("GM_CONV_SK")  # "0": the slices on the general cfg 11 tile kernel (round-3 path) instead of conv_sk.hip -- A/B measurements only
 DMA_CFGS = (11, 14, 15, 16, 17, 18, 19, 24, 25)
 # cfg 24 (csrc/conv_sn.hip, round 6): a small volume's 3x3x3 convolution K-COMPLETE on 16-channel output blocks -- 256 voxels x 16 channels per work-group, the
@@ -739,21 +740,20 @@ NARROW_N_MAX_CHUNKS = int(os.environ.get("GM_CONV_SN_MAX_CHUNKS", "6"))
 # cfg 25: the same kernel over IMAGES (2-D 3x3 stride-1 convolutions, also over a nearest-2x up-sampled input): 16 x 16 pixels x 16 channels per work-group with the
 # in-LDS GroupNorm + SiLU prologue, the two-source input, the fused 1x1 shortcut and the statistics -- where the register-staged 2-D kernels took a separate
 # gn_stats / gn_apply / shortcut launch each (BASELINE configs[0], the 2-D DDPM UNet).  Up to NARROW_N_2D_MAX_FLOP per convolution (what was measured).
-NARROW_N_2D = os.environ.get("GM_CONV_SN2D", "1") != "0"
+NARROW_N_2D = True
 # conv_in of a 2-D network (C_in <= 4, 3x3, stride 1) on the C_in <= 4 edge kernel (cfg 12) as a depth-1 volume: BASELINE configs[0]'s 1 -> 32 at 16 x 64 x 64 ran
 # on the generic tile kernel (27 us, the longest launch of that forward, and a stand-alone statistics pass behind it)
-EDGE_2D_AS_3D = os.environ.get("GM_CONV_EDGE2D", "1") != "0"
-NARROW_N_2D_MAX_FLOP = float(os.environ.get("GM_CONV_SN2D_MAX_FLOP", "3e10"))
+EDGE_2D_AS_3D = True
+NARROW_N_2D_MAX_FLOP = 3e10
 # ... and the stride-2 Downsample convolution of a 2-D UNet on the same kernel (the stride-1 result's even positions: conv_sn.hip), statistics fused
-NARROW_N_2D_STRIDE2 = os.environ.get("GM_CONV_SN2D_STRIDE2", "1") != "0"
+NARROW_N_2D_STRIDE2 = True
 NARROW_HEAD_MAX_FLOP = 1.0e9
 # (Rounds 4-5 built three more tile structures on v_mfma_f32_32x32x16_bf16 -- cfg 21: 16-channel half-chunks, three work-groups per CU; cfg 22: 512-voxel
 #  tiles with 16-channel weight panels; cfg 23: cfg 22's image on four waves of 4 x 2 blocks -- each verified bit-level and measured: all tie or lose against
 #  cfg 14 in time, and in round 6 in JOULES per launch on every C2 shape (profiles/r06_taploop_energy.txt: +1 ... +16 %).  They live under experiments/
 #  with their host replays, not in the library.)
-COUT1_MARCH = os.environ.get("GM_CONV_COUT1_MARCH", "1") != "0"  # C_out == 1 heads: the depth-marching kernel (cfg 20) before the tile kernel (cfg 13)
+COUT1_MARCH = True  # C_out == 1 heads: the depth-marching kernel (cfg 20) before the tile kernel (cfg 13)
 DMA_WIDE_WAVES = os.environ.get("GM_CONV_WIDE_WAVES", "1") != "0"  # prefer cfg 14 (4 waves x 64 voxels) for large prologue-free stride-1 convolutions
-DMA_WIDE_WAVES_PRE = os.environ.get("GM_CONV_WIDE_WAVES_PRE", "0") != "0"  # ... also with the fused in-LDS prologue (its cfg 14 instantiation)
 DMA_WIDE_WAVE_MIN_TILES = 512                                       # ... from one full wave of work-groups on (2 per CU)
 
 
@@ -839,8 +839,8 @@ def _cfg_tile(cfg: int):
 
 COUT1_MARCH_LTD = os.environ.get("GM_CONV_COUT1_LTD")  # bench only: pin the depth-segment length (log2 planes) of configuration 20
 # log2 of the output columns a configuration-20 work-group walks over 128-byte rows: 5 = 8 x 32 (one work-group per CU, halo 1.33), 4 = 8 x 16 (69 KiB of
-# LDS: two work-groups per CU, halo 1.41; round 5 A/B: GM_CONV_COUT1_LTW)
-COUT1_MARCH_LTW_128B = int(os.environ.get("GM_CONV_COUT1_LTW", "4"))  # measured (gpurun r5v2): C2 out head 0.197-0.200 -> 0.139 ms
+# LDS: two work-groups per CU, halo 1.41; round 5 A/B)
+COUT1_MARCH_LTW_128B = 4  # measured in round 5: C2 out head 0.197-0.200 -> 0.139 ms
 
 
 _CONV_DEBUG_FLAGS = 0  # tools/bench_conv.py ablations only
@@ -854,11 +854,16 @@ SMALL_LINEAR_ROWS = 64       # 1x1 "convolutions" over at most this many rows ta
 TOKEN_GEMM = os.environ.get("GM_TOKEN_GEMM", "1") != "0"
 TOKEN_GEMM_MAX_ROWS = int(os.environ.get("GM_TOKEN_GEMM_MAX_ROWS", "32768"))  # (8192 until the wide form of round 6: small_ops.hip token_gemm_wide_kernel)
 TOKEN_GEMM_MAX_CIN = 512
-TOKEN_GEMM_MAX_FLOP = float(os.environ.get("GM_TOKEN_GEMM_MAX_FLOP", "2.0e9"))
+TOKEN_GEMM_MAX_FLOP = 2.0e9
 DMA_CONV = True              # route eligible 3x3x3 convolutions through conv_dma.hip (cfg 11)
 DMA_CONV_MIN_VOXELS = 1 << 8
 LDS_SOFT_LIMIT = 80 * 1024   # two workgroups per CU
 LDS_HARD_LIMIT = 160 * 1024
+
+
+# the LDS-DMA kernels (and the C_in <= 4 edge kernel) are built for fixed tiles; extents below the tile are masked (W = 8 at the 8^3 level: half the tile idles,
+# still 2x faster than cfg 4)
+_FIXED_TILE_BITS = {11: (2, 2, 4), 12: (2, 2, 4), 14: (2, 2, 4), 15: (1, 2, 4), 16: (3, 2, 4), 18: (3, 2, 4), 19: (3, 2, 4), 24: (2, 2, 4), 25: (0, 4, 4)}
 
 
 def _choose_conv_cfg(desc: GmConvDesc, n_vox_out: int, force_cfg: Optional[int] = None, only: Optional[tuple] = None, exclude: tuple = ()):
@@ -885,8 +890,7 @@ def _choose_conv_cfg(desc: GmConvDesc, n_vox_out: int, force_cfg: Optional[int] 
         # (cfg 14: two operand register sets, software-pipelined tap loop -- 256 registers per wave) is 2-9 % faster than the 8-wave x 32-voxel
         # form (cfg 11, 128 registers: one operand set) on every C2 / C3 shape once the grid fills the chip (profiles/r02_conv_tile_configs_v2.txt);
         # cfg 11 keeps the fused-prologue instantiation (the cfg 14 one spills) and the small grids (its split-K form).
-        tiles = desc.N * -(-desc.Do // 4) * -(-desc.Ho // 4) * -(-desc.Wo // 16) * -(-cout // 64)
-        wide = (bool(desc.pre_scale is None or not desc.pre_scale) or DMA_WIDE_WAVES_PRE) and tiles >= DMA_WIDE_WAVE_MIN_TILES and DMA_WIDE_WAVES
+        wide = not desc.pre_scale and _conv_tiles(desc.N, (desc.Do, desc.Ho, desc.Wo), cout) >= DMA_WIDE_WAVE_MIN_TILES and DMA_WIDE_WAVES
         order = ([15] if desc.sd == 2 else ([14, 11] if wide else [11])) + order
         # (512-voxel tiles -- cfg 16 / 18, one work-group per CU, half the weight-panel traffic -- measure within +-5 % of two 256-voxel
         # work-groups in isolation and 5-15 % slower on the 64 -> 64 layers inside the forward: profiles/r02_conv_tile_configs.txt,
@@ -902,9 +906,10 @@ def _choose_conv_cfg(desc: GmConvDesc, n_vox_out: int, force_cfg: Optional[int] 
     order = [c for c in order if (only is None or c in only) and c not in exclude]
     best = None
     for cfg in order:
-        bm, _ = _cfg_tile(cfg)
-        tb = _tile_bits_fast if cfg >= 5 else _tile_bits
-        bits = tb(bm.bit_length() - 1, (desc.Do, desc.Ho, desc.Wo))
+        bits = _FIXED_TILE_BITS.get(cfg)
+        if bits is None:
+            bm, _ = _cfg_tile(cfg)
+            bits = (_tile_bits_fast if cfg >= 5 else _tile_bits)(bm.bit_length() - 1, (desc.Do, desc.Ho, desc.Wo))
         if cfg == 20:
             # rows of 128 bytes walk 8 x 32 output columns, rows of 256 bytes 8 x 16; the depth segment of a work-group (2^ltd planes, halo
             # overhead (2^ltd + 2) / 2^ltd) is the longest that still gives every CU a work-group
@@ -917,8 +922,6 @@ def _choose_conv_cfg(desc: GmConvDesc, n_vox_out: int, force_cfg: Optional[int] 
             if COUT1_MARCH_LTD is not None:
                 ltd = int(COUT1_MARCH_LTD)
             bits = [ltd, 3, ltw]
-        if cfg in (11, 12, 14, 15, 16, 18, 19, 24, 25):  # the LDS-DMA kernels (and the C_in <= 4 edge kernel) are built for fixed tiles; extents below the tile are masked (W = 8 at the
-            bits = {11: [2, 2, 4], 12: [2, 2, 4], 14: [2, 2, 4], 15: [1, 2, 4], 16: [3, 2, 4], 18: [3, 2, 4], 19: [3, 2, 4], 24: [2, 2, 4], 25: [0, 4, 4]}[cfg]  # 8^3 level: half the tile idles, still 2x faster than cfg 4)
         desc.cfg, desc.ltd, desc.lth, desc.ltw = cfg, bits[0], bits[1], bits[2]
         lds = lib().gm_conv_lds_bytes(C.byref(desc))  # -1: configuration not applicable to this geometry
         soft = LDS_HARD_LIMIT if cfg >= 5 else LDS_SOFT_LIMIT  # the fast kernels are sized for their own occupancy
@@ -941,52 +944,62 @@ def _attach_conv_stats(d: GmConvDesc, out: torch.Tensor, n: int, cout: int) -> N
         out._gm_cstats = cst
 
 
+def _out_and_res(out_shape, dtype, device, out, res):
+    """`out` allocated or checked, `res` checked against it: the same for every route.  -> (out, its leading dim)."""
+    if out is not None and (tuple(out.shape) != out_shape or out.dtype != dtype):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {out_shape}")
+    if res is not None and (tuple(res.shape) != out_shape or res.dtype != dtype):
+        raise ValueError(f"residual has shape {tuple(res.shape)} / {res.dtype}, expected {out_shape} / {dtype}")
+    if out is None:
+        return torch.empty(out_shape, dtype=dtype, device=device), out_shape[-1]  # (dense: the leading dim is the channel count)
+    return out, arena_ld(out)
+
+
+def _epilogue_into(d: GmConvDesc, n, cout, out, out_ld, res, rowvec, bias, post_act):
+    """Bias, rowvec, residual, output and post-activation of a tile-kernel launch into a fresh (zeroed) descriptor; `out` / `res` have been checked
+    (_out_and_res).  Returns the fp32 bias: the caller keeps it alive until the launch is enqueued."""
+    b32 = as_f32(bias)
+    d.bias = _ptr(b32)
+    if rowvec is not None:
+        if rowvec.dtype != torch.float32 or rowvec.dim() != 2 or rowvec.shape[1] != cout or rowvec.shape[0] not in (1, n):
+            raise ValueError(f"rowvec must be fp32 [1 or N, Cout], got {tuple(rowvec.shape)} {rowvec.dtype}")
+        if rowvec.stride(1) != 1:
+            raise ValueError("rowvec must have unit stride on its last dim")
+        d.rowvec, d.rowvec_bstride = rowvec.data_ptr(), (0 if rowvec.shape[0] == 1 else rowvec.stride(0))
+    if res is not None:
+        d.res, d.res_ld = res.data_ptr(), arena_ld(res)
+    d.y, d.y_ld = out.data_ptr(), out_ld
+    d.post_act, d.debug_flags = POST_ACT[post_act], _CONV_DEBUG_FLAGS
+    return b32
+
+
+def _geometry_into(d: GmConvDesc, n, cin, cout, src, out_sp, k, stride, pad, dil, dtype) -> None:
+    d.N, d.Cin, d.Cout = n, cin, cout
+    d.Ds, d.Hs, d.Ws = src
+    d.Do, d.Ho, d.Wo = out_sp
+    d.kd, d.kh, d.kw = k
+    d.sd, d.sh, d.sw = stride
+    d.pd, d.ph, d.pw = pad
+    d.dd, d.dh, d.dw = dil
+    d.dtype = dt_code(dtype)
+
+
 def _conv_subpixel(x, weight, bias, rowvec, res, post_act, out, want_stats, n, cin, cout, src, packed=None, label="mode3 (executed flops: 8 of the 27 taps)"):
     """Nearest-2x up-sampling + 3x3x3 convolution as 8 sub-pixel 2x2x2 convolutions (GmConvDesc.in_mode 3, configuration 17).
     Returns None when the geometry is not covered (the caller falls back to the folded up-sampling path)."""
     dtype = x.dtype
     out_sp = tuple(2 * v for v in src)
-    out_shape = (n, *out_sp, cout)
-    if out is None:
-        out = torch.empty(out_shape, dtype=dtype, device=x.device)
-    elif tuple(out.shape) != out_shape or out.dtype != dtype:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {out_shape}")
+    out, out_ld = _out_and_res((n, *out_sp, cout), dtype, x.device, out, res)
     d = GmConvDesc()
     if packed is None:
         packed = packed_subpixel_weight(weight, dtype)
     d.in_mode, d.fd, d.fh, d.fw = 3, 2, 2, 2
     d.x, d.x_ld, d.w = x.data_ptr(), arena_ld(x), packed.data_ptr()
-    b32 = as_f32(bias) if bias is not None else None
-    d.bias = _ptr(b32)
-    d.pre_scale = d.pre_shift = None
-    if rowvec is not None:
-        if rowvec.dtype != torch.float32 or rowvec.dim() != 2 or rowvec.shape[1] != cout or rowvec.shape[0] not in (1, n) or rowvec.stride(1) != 1:
-            raise ValueError(f"rowvec must be fp32 [1 or N, Cout], got {tuple(rowvec.shape)} {rowvec.dtype}")
-        d.rowvec, d.rowvec_bstride = rowvec.data_ptr(), (0 if rowvec.shape[0] == 1 else rowvec.stride(0))
-    else:
-        d.rowvec, d.rowvec_bstride = None, 0
-    if res is not None:
-        if tuple(res.shape) != out_shape or res.dtype != dtype:
-            raise ValueError(f"residual has shape {tuple(res.shape)} / {res.dtype}, expected {out_shape} / {dtype}")
-        d.res, d.res_ld = res.data_ptr(), arena_ld(res)
-    else:
-        d.res, d.res_ld = None, 0
-    d.y, d.y_ld = out.data_ptr(), arena_ld(out)
-    d.skip_w = d.skip_bias = None
-    d.skip_x[0] = d.skip_x[1] = None
-    d.N, d.Cin, d.Cout = n, cin, cout
-    d.Ds, d.Hs, d.Ws = src
-    d.Do, d.Ho, d.Wo = out_sp
-    d.kd = d.kh = d.kw = 2
-    d.sd = d.sh = d.sw = 1
-    d.pd = d.ph = d.pw = 0
-    d.dd = d.dh = d.dw = 1
-    d.pre_act, d.post_act, d.dtype = 0, POST_ACT[post_act], dt_code(dtype)
-    d.debug_flags = _CONV_DEBUG_FLAGS
+    b32 = _epilogue_into(d, n, cout, out, out_ld, res, rowvec, bias, post_act)  # noqa: F841 -- alive until the launch
+    _geometry_into(d, n, cin, cout, src, out_sp, (2, 2, 2), _ONES, _ZEROS, _ONES, dtype)
     d.cfg, d.ltd, d.lth, d.ltw = 17, 2, 2, 4
     if lib().gm_conv_lds_bytes(C.byref(d)) <= 0:
         return None
-    d.stats = None
     if want_stats:
         _attach_conv_stats(d, out, n, cout)
     nvo = n * math.prod(out_sp)
@@ -1000,8 +1013,8 @@ def _conv_subpixel(x, weight, bias, rowvec, res, post_act, out, want_stats, n, c
     return out
 
 
-STRIDE2_DGRAD_SUBPIXEL = os.environ.get("GM_CONV_STRIDE2_DGRAD", "1") != "0"
-TRANSPOSED_S2_SUBPIXEL = os.environ.get("GM_CONV_TRANSPOSED_S2_SUBPIXEL", "1") != "0"
+STRIDE2_DGRAD_SUBPIXEL = True
+TRANSPOSED_S2_SUBPIXEL = True
 
 
 def conv_stride2_dgrad(gy: torch.Tensor, weight: torch.Tensor, x_spatial: Sequence[int], pad_lo: int) -> Optional[torch.Tensor]:
@@ -1019,6 +1032,382 @@ def conv_stride2_dgrad(gy: torch.Tensor, weight: torch.Tensor, x_spatial: Sequen
     packed = packed_stride2_dgrad_weight(weight, gy.dtype, pad_lo)
     return _conv_subpixel(gy, weight, None, None, None, "none", None, False, n, cg, weight.shape[1], src, packed=packed,
                           label="stride-2 data gradient as 8 sub-pixel 2x2x2 convolutions")
+
+
+# ---- ops.conv: geometry -> operand facts -> the ordered routes -> the plan of the tile kernels -> its execution -------------------------------------
+# The geometry of one call as plain integers, three spatial axes (missing leading ones: extent / kernel / stride / dilation 1, padding 0).  src: input extents;
+# k, s, plo, phi, dil, opad: kernel, stride, low / high padding, dilation, output_padding; out_sp, conv_pad, conv_stride, in_mode, f = (fd, fh, fw): what the
+# descriptor of a tile kernel takes (a transposed convolution is a stride-1 one over the zero-inserted input, up-sampling is folded into the indexing);
+# es: bytes per element; vecw: elements per 16 bytes; rows = N x input voxels.
+ConvGeometry = namedtuple("ConvGeometry", "nsp n cin cout src k s plo phi dil opad upsample transposed out_sp conv_pad conv_stride in_mode f es vecw rows bf16")
+# What the routing rules need to know about the operands of that call -- facts, no tensors.  cat: the input is a VirtualCat whose first part has cin0 channels;
+# x_ld / x_vec: leading dim of x, and whether it and the pointer are 16-byte aligned; weight_dim: dims of the weight tensor (0: only a packed panel came);
+# w333: configuration 12 can derive its K-major image (a [Cout, Cin, 3, 3, 3] weight, not transposed); pre: None, "tables" or "recipe" -- a GnRecipe whose
+# finalisation has not run, recipe = (its n, part channels, groups, rows of its tables); rowvec / res / vt: the operand is there; skip_cin: channels of the
+# shortcut's parts; gn_fused: fuse_gn_prologue(x) when there is a prologue.
+ConvFacts = namedtuple("ConvFacts", "cat cin0 x_ld x_vec weight_dim w333 packed pre recipe pre_act post_act rowvec res vt want_stats skip_cin force_cfg ksplit "
+                                    "allow_subpixel gn_fused")
+# What _plan_tile_kernels decides beyond the configuration and tile bits it leaves on the descriptor.  fallback: None (launch the descriptor), "two_pass" or
+# "shortcut_first"; ksplit / workspace: K slices (0: not split) and the bytes of their partials; recipe_at: where a pending GroupNorm is finalised --
+# "descriptor" (cfg 24 / 25 prologue), "slices" (the K slices of conv_sk.hip), "launch" (gm_gn_finalize_channels), None (no pending recipe).
+ConvPlan = namedtuple("ConvPlan", "fallback ksplit workspace recipe_at")
+_ONES, _ZEROS = (1, 1, 1), (0, 0, 0)
+
+
+def _conv_geometry(x, x2, weight, packed, cout, kernel, stride, padding, pad_hi, dilation, upsample, transposed, output_padding) -> ConvGeometry:
+    nsp = x.dim() - 2
+    if nsp < 1 or nsp > 3:
+        raise ValueError("conv expects (N, *spatial, C) with 1-3 spatial axes")
+
+    def axes(v, fill):
+        v = tuple(v) if isinstance(v, (tuple, list)) else (int(v),) * nsp
+        if len(v) != nsp:
+            raise ValueError("per-axis argument has the wrong length")
+        return (fill,) * (3 - nsp) + v
+    k, s, plo = axes(kernel, 1), axes(stride, 1), axes(padding, 0)
+    phi, dil, opad = plo if pad_hi is None else axes(pad_hi, 0), axes(dilation, 1), axes(output_padding, 0)
+    n, cin = x.shape[0], x.shape[-1] + (0 if x2 is None else x2.shape[-1])
+    src = (1,) * (3 - nsp) + tuple(x.shape[1:-1])
+    if x2 is not None and (x2.shape[:-1] != x.shape[:-1] or x2.dtype != x.dtype):
+        raise ValueError("the two parts of a concatenated input must agree outside the channel dim")
+    if packed is None:
+        cout = weight.shape[1] if transposed else weight.shape[0]
+        wcin = weight.shape[0] if transposed else weight.shape[1]
+        if wcin != cin:
+            raise ValueError(f"input has {cin} channels but the weight expects {wcin}")
+    in_mode, f = 0, _ONES
+    if transposed:
+        if s != _ONES:  # (stride 1: no zero insertion -- a plain convolution with the flipped, in/out-swapped panel: every fast kernel applies; this is the
+            in_mode, f = 2, s  # data gradient of the stride-1 convolutions)
+        out_sp = tuple([(src[i] - 1) * s[i] - plo[i] - phi[i] + dil[i] * (k[i] - 1) + opad[i] + 1 for i in (0, 1, 2)])
+        conv_pad, conv_stride = tuple([dil[i] * (k[i] - 1) - plo[i] for i in (0, 1, 2)]), _ONES
+    else:
+        if upsample:
+            in_mode, f = 1, (1,) * (3 - nsp) + (2,) * nsp
+        out_sp = src  # (1x1, the GEMM routes: nothing to compute)
+        if k != _ONES or s != _ONES or plo != _ZEROS or phi != _ZEROS or upsample:
+            out_sp = tuple([(src[i] * f[i] + plo[i] + phi[i] - dil[i] * (k[i] - 1) - 1) // s[i] + 1 for i in (0, 1, 2)])
+        conv_pad, conv_stride = plo, s
+    es = x.element_size()
+    return ConvGeometry._make((nsp, n, cin, cout, src, k, s, plo, phi, dil, opad, upsample, transposed, out_sp, conv_pad, conv_stride, in_mode, f, es, 16 // es,
+                               n * math.prod(src), x.dtype == torch.bfloat16))
+
+
+# ---- the routes in front of the tile kernels, in the order ops.conv asks them: one predicate over (geometry, facts) + one launcher each ---------------
+# a handful of rows (decode steps, the timestep MLP): the barrier-free small-row GEMM instead of the tiled kernel
+def _takes_small_rows(g: ConvGeometry, f: ConvFacts) -> bool:
+    return (g.rows <= SMALL_LINEAR_ROWS and not f.cat and g.k == _ONES and g.s == _ONES and not g.transposed and not g.upsample and f.pre is None
+            and not f.rowvec and not f.want_stats and f.skip_cin is None and f.force_cfg is None and g.cin % g.vecw == 0 and f.x_vec
+            and g.plo == _ZEROS and g.phi == _ZEROS)
+
+
+def _launch_small_rows(g, f, x, panel, bias, pre_act, res, post_act, out):
+    dtype = x.dtype
+    out, out_ld = _out_and_res((*x.shape[:-1], g.cout), dtype, x.device, out, res)
+    b32 = as_f32(bias)
+    _timed(f"linear_rows<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * g.rows * g.cin * g.cout, bytes=float(g.es * g.cin * g.cout), shape=f"{g.rows}x{g.cin}->{g.cout}"),
+           lambda: check(lib().gm_linear_rows(x.data_ptr(), f.x_ld, panel().data_ptr(), _ptr(b32), _ptr(res), 0 if res is None else arena_ld(res),
+                                              out.data_ptr(), out_ld, g.rows, g.cin, g.cout, ACT[pre_act], POST_ACT[post_act], dt_code(dtype),
+                                              _stream()), "gm_linear_rows"))
+    return out
+
+
+# conv_in of a 2-D network (C_in <= 4): the taps x inputs ARE the GEMM K of the edge kernel (cfg 12, conv_edge.hip) -- handed over as the depth-1 volume
+# it is, the 3x3 kernel as the centre plane of a 3x3x3 one (zero planes in front of and behind it meet the padding planes only)
+def _takes_edge_2d(g: ConvGeometry, f: ConvFacts) -> bool:
+    return (EDGE_2D_AS_3D and g.nsp == 2 and not f.cat and not f.packed and f.weight_dim == 4 and not g.transposed and not g.upsample
+            and g.cin <= 4 and g.k == (1, 3, 3) and g.s == _ONES and g.dil == _ONES and g.plo == (0, 1, 1) and g.phi == (0, 1, 1) and f.pre is None
+            and f.pre_act == "none" and f.skip_cin is None and f.force_cfg is None and f.ksplit is None and g.cout % g.vecw == 0 and g.rows >= DMA_CONV_MIN_VOXELS)
+
+
+def _launch_edge_2d(x, weight, bias, rowvec, res, post_act, out, want_stats):
+    """Re-enters conv with the volume; the statistics end up on the tensor the caller receives."""
+    def embed():
+        w5 = torch.zeros((weight.shape[0], weight.shape[1], 3, 3, 3), dtype=weight.dtype, device=weight.device)
+        w5[:, :, 1] = weight.detach()
+        return w5
+    got = conv(x.unsqueeze(1), _cached(weight, ("centre_plane_3d",), embed), bias, kernel=3, padding=1, rowvec=rowvec,
+               res=None if res is None else res.unsqueeze(1), post_act=post_act, out=None if out is None else out.unsqueeze(1), want_stats=want_stats)
+    y = out if out is not None else got.squeeze(1)
+    st = getattr(got, "_gm_cstats", None)
+    if st is not None:
+        y._gm_cstats = st
+    return y
+
+
+def _takes_token_gemm(g: ConvGeometry, f: ConvFacts) -> bool:
+    return (TOKEN_GEMM and SMALL_LINEAR_ROWS < g.rows <= TOKEN_GEMM_MAX_ROWS and g.cin <= TOKEN_GEMM_MAX_CIN and 2.0 * g.rows * g.cin * g.cout <= TOKEN_GEMM_MAX_FLOP
+            and not f.cat and g.k == _ONES and g.s == _ONES and not g.upsample and not f.rowvec and not f.want_stats and f.skip_cin is None
+            and f.force_cfg is None and f.ksplit is None and g.cin % g.vecw == 0 and f.x_vec and g.plo == _ZEROS and g.phi == _ZEROS and g.opad == _ZEROS)
+
+
+# vt = (workspace, first V channel, head dim): the stacked q | k | v projection of an attention block also stores the transposed V image of the LDS-DMA
+# attention kernel (one pack launch less per block); the caller finds `_gm_vt_packed` on the result
+def _token_gemm_stores_vt(g: ConvGeometry, f: ConvFacts) -> bool:
+    return f.vt and not f.res and f.post_act == "none" and g.bf16 and (g.rows // g.n) % 64 == 0
+
+
+# the GroupNorm is still a recipe (short statistic tables): the wide token GEMM finalises it in its prologue -- no launch for the norm
+def _token_gemm_takes_recipe(g: ConvGeometry, f: ConvFacts) -> bool:
+    if not (GN_IN_TOKEN_GEMM and f.pre == "recipe" and not g.transposed):
+        return False
+    rn, cs, groups, table_rows = f.recipe
+    return (rn == g.n and sum(cs) == g.cin and g.cin <= 384 and g.cin % (64 // g.es) == 0 and g.cout >= 32 and (g.rows // g.n) % 64 == 0
+            and g.cin % groups == 0 and all(r <= GN_IN_CONSUMER_MAX_ROWS for r in table_rows) and (not f.vt or _token_gemm_stores_vt(g, f)))
+
+
+def _launch_token_gemm(g, f, x, panel, bias, pre, pre_act, res, post_act, out, vt):
+    """-> (out, launched).  Not launched: (scale, shift) tables the kernels cannot read as vectors -- the caller goes on to the tile kernels with `out` allocated."""
+    dtype, n, rows, cin, cout = x.dtype, g.n, g.rows, g.cin, g.cout
+    out, out_ld = _out_and_res((*x.shape[:-1], cout), dtype, x.device, out, res)
+    b32 = as_f32(bias)
+    store_vt = _token_gemm_stores_vt(g, f)
+    vws, vt_c0, vt_dh = vt if store_vt else (None, 0, 0)
+    res_ld = 0 if res is None else arena_ld(res)
+
+    def launch(form, name, call):
+        if _PROFILE is None:
+            check(call(), name)
+        else:
+            _timed(f"token_gemm<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(g.es * (rows * (cin + cout) + cin * cout)),
+                                                                  shape=f"{rows}x{cin}->{cout}{form}"), lambda: check(call(), name))
+        if store_vt:
+            out._gm_vt_packed = True
+        return out, True
+    if _token_gemm_takes_recipe(g, f):
+        t = GmGnTables()
+        for i, st in enumerate(pre.stats):
+            t.stats[i], t.S[i], t.C[i] = st.data_ptr(), st.shape[0], pre.cs[i]
+        t.gamma, t.beta, t.eps, t.groups = _ptr(pre.gamma), _ptr(pre.beta), pre.eps, pre.groups
+        return launch(f" (GroupNorm from statistics{' +V^T image' if store_vt else ''})", "gm_linear_rows_gn", lambda: lib().gm_linear_rows_gn(
+            x.data_ptr(), f.x_ld, C.byref(t), n, rows // n, panel().data_ptr(), _ptr(b32), _ptr(res), res_ld, out.data_ptr(), out_ld, rows, cin, cout,
+            ACT[pre_act], POST_ACT[post_act], _ptr(vws), int(vt_c0), int(vt_dh), dt_code(dtype), _stream()))
+    sc = sh = None
+    if pre is not None:
+        sc, sh = pre
+        if sc.dtype != torch.float32 or sh.dtype != torch.float32 or sc.shape != (n, cin) or sh.shape != (n, cin) or sc.stride(-1) != 1 or sh.stride(-1) != 1 \
+                or sc.stride(0) != sh.stride(0):
+            raise ValueError("pre = (scale, shift): fp32 [N, Cin] tables with a common row pitch")
+        if not (sc.stride(0) % 4 == 0 and sc.data_ptr() % 16 == 0 and sh.data_ptr() % 16 == 0):
+            return out, False
+    pitch = 0 if sc is None else sc.stride(0)
+    if store_vt:
+        return launch(" (+V^T image)", "gm_linear_rows_affine_vt", lambda: lib().gm_linear_rows_affine_vt(
+            x.data_ptr(), f.x_ld, _ptr(sc), _ptr(sh), pitch, rows // n, panel().data_ptr(), _ptr(b32), out.data_ptr(), out_ld, rows, cin, cout,
+            ACT[pre_act], vws.data_ptr(), int(vt_c0), int(vt_dh), dt_code(dtype), _stream()))
+    return launch("", "gm_linear_rows_affine", lambda: lib().gm_linear_rows_affine(
+        x.data_ptr(), f.x_ld, _ptr(sc), _ptr(sh), pitch, rows // n, panel().data_ptr(), _ptr(b32), _ptr(res), res_ld, out.data_ptr(), out_ld, rows, cin,
+        cout, ACT[pre_act], POST_ACT[post_act], dt_code(dtype), _stream()))
+
+
+def _subpixel_operands(g: ConvGeometry, f: ConvFacts) -> bool:
+    """What both sub-pixel routes (configuration 17) ask of a 3-D call besides their geometry."""
+    return (not f.cat and g.nsp == 3 and g.dil == _ONES and f.pre is None and f.pre_act == "none" and f.skip_cin is None and f.force_cfg is None
+            and f.weight_dim > 0 and g.cin % (64 // g.es) == 0 and g.cout % g.vecw == 0 and f.x_vec and g.rows >= DMA_CONV_MIN_VOXELS)
+
+
+def _takes_subpixel_upsample(g: ConvGeometry, f: ConvFacts) -> bool:
+    return (g.upsample and SUBPIXEL_UPSAMPLE and f.allow_subpixel and g.k == (3, 3, 3) and g.s == _ONES and g.plo == _ONES and g.phi == _ONES
+            and _subpixel_operands(g, f))
+
+
+# nn.ConvTranspose3d(stride 2) whose output is exactly twice the input (VQ-VAE up-sampling k = 4 / pad 1, the AutoencoderKL's optional ConvTranspose
+# k = 3 / pad 1 / output_padding 1, the data gradient of the Downsample convolutions): 8 sub-pixel 2x2x2 convolutions, one launch of configuration 17 --
+# no zero-inserted operand, no gather
+def _takes_transposed_subpixel(g: ConvGeometry, f: ConvFacts) -> bool:
+    return (g.transposed and TRANSPOSED_S2_SUBPIXEL and g.s == (2, 2, 2) and g.k in ((3, 3, 3), (4, 4, 4)) and g.plo[0] == g.plo[1] == g.plo[2]
+            and stride2_subpixel_covers(g.k[0], g.plo[0]) and g.out_sp == tuple(2 * v for v in g.src) and _subpixel_operands(g, f))
+
+
+# ---- the tile kernels: descriptor, plan, execution -----------------------------------------------------------------------------------------------------
+def _recipe_fits_prologue(g: ConvGeometry, f: ConvFacts) -> bool:
+    """A GroupNorm whose finalisation has not run, in front of a convolution whose kernel might do it in its prologue (cfg 24 / 25, the K slices of cfg 11)."""
+    if f.pre != "recipe" or not NARROW_N:
+        return False
+    rn, cs, _, _ = f.recipe
+    return sum(cs) == g.cin and rn == g.n and g.k[-2:] == (3, 3) and g.s == _ONES and not g.transposed and not g.upsample and (not f.cat or cs[0] == f.cin0)
+
+
+def _tile_descriptor(g, f, x, x2, panel, bias, pre, pre_act, rowvec, res, post_act, out, out_ld, skip):
+    """-> (descriptor with operands and geometry filled, no configuration yet; the derived tensors it points to)."""
+    n, cin, cout, dtype = g.n, g.cin, g.cout, x.dtype
+    d = GmConvDesc()
+    d.in_mode, (d.fd, d.fh, d.fw) = g.in_mode, g.f
+    d.x, d.x_ld, d.w = x.data_ptr(), f.x_ld, panel.data_ptr()
+    if x2 is not None:
+        d.x2, d.x2_ld, d.cin_split = x2.data_ptr(), arena_ld(x2), f.cin0
+    keep = [panel, _epilogue_into(d, n, cout, out, out_ld, res, rowvec, bias, post_act)]
+    if _recipe_fits_prologue(g, f):
+        # the configuration is chosen as if (scale, shift) existed (a readable, aligned stand-in); the tables go into the descriptor once the plan says
+        # which kernel finalises the norm, anything else materialises them
+        d.pre_scale = d.pre_shift = pre.stats[0].data_ptr()
+    elif pre is not None:
+        sc, sh = pre
+        require_device(sc, sh)
+        if tuple(sc.shape) != (n, cin) or sc.dtype != torch.float32:
+            raise ValueError("pre scale/shift must be fp32 [N, Cin]")
+        d.pre_scale, d.pre_shift = sc.data_ptr(), sh.data_ptr()
+    if skip is not None:
+        parts, sw, sb = skip
+        parts = list(parts)
+        require_device(sw, sb, *parts)
+        if res is not None:
+            raise ValueError("skip and res are exclusive (the shortcut IS the residual)")
+        if not 1 <= len(parts) <= 2 or sw.shape[0] != cout or sw.shape[1] != sum(t.shape[-1] for t in parts) or math.prod(sw.shape[2:]) != 1:
+            raise ValueError("skip = (1 or 2 parts, [Cout, sum(C_part), 1...] weight, bias)")
+        for i, t in enumerate(parts):
+            if tuple(t.shape[:-1]) != tuple(out.shape[:-1]) or t.dtype != dtype:
+                raise ValueError("skip parts must have the output geometry and dtype")
+            d.skip_x[i], d.skip_ld[i], d.skip_cin[i] = t.data_ptr(), arena_ld(t), t.shape[-1]
+        keep += [packed_conv_weight(sw, dtype), as_f32(sb)]
+        d.skip_w, d.skip_bias = keep[-2].data_ptr(), _ptr(keep[-1])
+    _geometry_into(d, n, cin, cout, g.src, g.out_sp, g.k, g.conv_stride, g.conv_pad, g.dil, dtype)
+    d.pre_act = ACT[pre_act]
+    return d, keep
+
+
+def _conv_tiles(n: int, out_sp, cout: int) -> int:
+    """Work-groups of an unsplit cfg 11 / 14 launch: 4 x 4 x 16 voxels x 64 output channels each."""
+    return n * -(-out_sp[0] // 4) * -(-out_sp[1] // 4) * -(-out_sp[2] // 16) * -(-cout // 64)
+
+
+def _split_slices(g: ConvGeometry, nchunks: int, ksplit: Optional[int]) -> int:
+    """Into how many K slices a cfg 11 launch over `nchunks` K chunks is split (<= 1: not at all).  ksplit None = the policy: below SPLITK_MAX_TILES work-groups,
+    as many slices as it takes to reach about SPLITK_TARGET_WGS.  No slice stays empty: 12 chunks over "8" slices = 6 slices of 2."""
+    if ksplit is None:
+        tiles = _conv_tiles(g.n, g.out_sp, g.cout)
+        ksplit = min(nchunks, SPLITK_MAX, SPLITK_TARGET_WGS // tiles) if tiles < SPLITK_MAX_TILES else 1
+    return -(-nchunks // -(-nchunks // ksplit)) if ksplit > 1 else ksplit
+
+
+def _covers(d: GmConvDesc, nvox: int, cfg: Optional[int]) -> bool:
+    """Try the LDS-DMA configurations (cfg None: the policy's order) on the descriptor: True = one covers the geometry and is now set."""
+    try:
+        _choose_conv_cfg(d, nvox, cfg, only=DMA_CFGS)
+        return True
+    except ValueError:
+        return False
+
+
+def _plan_tile_kernels(d: GmConvDesc, g: ConvGeometry, f: ConvFacts) -> ConvPlan:
+    """Which kernel, and how the prologue is applied -- from the descriptor (operands and geometry filled), the geometry and the operand facts alone; only the
+    host-side planners of the library are asked.  Leaves cfg, the tile bits and ksplit on the descriptor."""
+    # (1) an LDS-DMA configuration when it covers the geometry: fused shortcut, in-LDS prologue, both parts of a VirtualCat read in place;
+    # (2) else the operand is first reduced to ONE activated tensor where needed (two_pass: gn_apply passes; the shortcut as 1x1 launches first), and
+    # (3) the register-staged / generic kernels take what is left, with their own fused prologue for small tensors.
+    n, cin, cout, forced = g.n, g.cin, g.cout, f.force_cfg
+    nvox, bk = math.prod(g.out_sp), 64 // g.es
+    flop = 2.0 * n * nvox * cout * cin * math.prod(g.k)
+    fuse_in_lds = f.pre is None or DMA_FUSED_PROLOGUE in (True, "always", "1") or (DMA_FUSED_PROLOGUE == "auto" and flop <= DMA_FUSED_PROLOGUE_MAX_FLOP)
+    large = nvox * n >= DMA_CONV_MIN_VOXELS
+    dma_ok = False
+    if forced is not None and forced in DMA_CFGS or (forced is None and DMA_CONV and cout > 16 and large and fuse_in_lds):
+        dma_ok = _covers(d, nvox, forced)
+    if NARROW_N and forced is None and f.ksplit is None and DMA_CONV and fuse_in_lds and large:
+        if dma_ok and d.cfg == 11 and SPLITK:
+            deep = cin // bk + sum(f.skip_cin or ()) // bk
+            if _split_slices(g, cin // bk, None) > 1 and deep <= NARROW_N_MAX_CHUNKS and not _covers(d, nvox, 24):
+                _choose_conv_cfg(d, nvox, 11, only=DMA_CFGS)  # (the launch would be split over K: K-complete on 16-channel blocks instead, cfg 24, where it covers)
+        elif not dma_ok and cout <= 16 and (d.kd == 3 or NARROW_N_2D) and flop <= NARROW_HEAD_MAX_FLOP:
+            # a narrow output head of a SMALL problem (the latent UNet's 64 -> 4, the 2-D UNet's 32 -> 1): the generic tile kernel otherwise (42 us at 32^3); the
+            # C_out = 1 head of a large volume keeps its depth-marching kernel (cfg 20)
+            dma_ok = _covers(d, nvox, 24 if d.kd == 3 else 25)
+    recipe_at = None
+    if _recipe_fits_prologue(g, f):
+        if dma_ok and d.cfg in (24, 25):
+            recipe_at = "descriptor"
+        elif dma_ok and d.cfg == 11 and GN_IN_SPLIT_SLICES and (f.ksplit is not None or SPLITK):
+            recipe_at = "slices"  # as far as the launch is split (below): the K slices of conv_sk.hip finalise the norm themselves
+        else:
+            recipe_at = "launch"
+    if not dma_ok:
+        if forced is not None and forced in DMA_CFGS:
+            raise ValueError(f"configuration {forced} does not cover this convolution")
+        if f.cat:
+            return ConvPlan("two_pass", 0, 0, recipe_at)  # only the LDS-DMA kernels read a concatenated input in place
+        # (round 5: NOT the large 1x1 projections -- the q | k | v projection of C2's mid-block attention, 32 768 x 256 -> 768, is 102 us fused against
+        #  62 + 12 two-pass in isolation, and 0.109 against 0.081 + 0.035 inside the forward: nothing, profiles/r05_qkv_projection_c2.txt)
+        if f.pre is not None and forced is None and cout > 16 and math.prod(g.k) > 1 and not f.gn_fused:
+            return ConvPlan("two_pass", 0, 0, recipe_at)  # a large ResnetBlock convolution: the HBM-bound gm_gn_apply pass + the prologue-free kernel (which
+            # still fuses the shortcut) beats both the in-LDS and the register-staged prologue (GN_APPLY_POLICY, DMA_FUSED_PROLOGUE)
+        if f.skip_cin is not None:
+            return ConvPlan("shortcut_first", 0, 0, recipe_at)
+        _choose_conv_cfg(d, nvox, forced, exclude=(DMA_CFGS + (() if f.w333 else (12,))) if forced is None else ())  # (cfg 12 derives its image from the weight)
+    if d.cfg == 12 and not f.w333:
+        raise ValueError("configuration 12 needs the original [Cout, Cin, 3, 3, 3] weight (its K-major image is derived from it)")
+    ksplit = workspace = 0
+    if dma_ok and d.cfg == 11 and (f.ksplit is not None or SPLITK):
+        ks = _split_slices(g, cin // bk, f.ksplit)
+        if ks > 1:
+            d.ksplit = int(ks)
+            workspace = lib().gm_conv_splitk_workspace_bytes(C.byref(d))
+            if workspace > 0:
+                ksplit = d.ksplit
+            elif f.ksplit is not None:
+                raise ValueError(f"split-K by {ks} is not available for this convolution")
+            else:
+                d.ksplit = workspace = 0
+    if recipe_at == "slices" and not ksplit:
+        recipe_at = "launch"
+    return ConvPlan(None, ksplit, workspace, recipe_at)
+
+
+def _finalise_into(d: GmConvDesc, recipe: GnRecipe) -> None:
+    """The finalisation launch of a pending GroupNorm (once: cached on the recipe), its (scale, shift) into the descriptor."""
+    sc, sh = recipe.materialise()
+    d.pre_scale, d.pre_shift = sc.data_ptr(), sh.data_ptr()
+
+
+def _recipe_into_descriptor(d: GmConvDesc, recipe: GnRecipe) -> None:
+    """The pending GroupNorm as statistic tables in the descriptor (in place of the stand-in); the finalisation launch after all when the kernel does not
+    take that form (a table longer than the short form's bound, more channels than the LDS tables hold)."""
+    d.pre_scale = d.pre_shift = None
+    for i, st in enumerate(recipe.stats):
+        d.pre_stats[i], d.pre_S[i], d.pre_C[i] = st.data_ptr(), st.shape[0], recipe.cs[i]
+    d.pre_gamma, d.pre_beta, d.pre_eps, d.pre_groups = _ptr(recipe.gamma), _ptr(recipe.beta), recipe.eps, recipe.groups
+    if lib().gm_conv_lds_bytes(C.byref(d)) <= 0:
+        d.pre_stats[0] = d.pre_stats[1] = None
+        d.pre_S[0] = d.pre_S[1] = d.pre_C[0] = d.pre_C[1] = 0
+        _finalise_into(d, recipe)
+
+
+def _run_tile_kernel(d: GmConvDesc, g: ConvGeometry, f: ConvFacts, plan: ConvPlan, x, weight, pre, out):
+    """Execute a plan without a fallback: the recipe where the plan put it, the split-K workspace, the statistics table, the launch."""
+    global _SK_STAMPS
+    if plan.recipe_at == "descriptor":
+        _recipe_into_descriptor(d, pre)
+    if d.cfg == 12:  # configuration 12 reads its weight fragments from the K-major image
+        cin_keep = packed_cin_weight(weight, x.dtype)
+        d.w = cin_keep.data_ptr()
+    kpart = None
+    if plan.ksplit > 1:
+        if _SK_KERNEL is not None:
+            lib().gm_conv_sk_set_enabled(int(_SK_KERNEL))
+        stamp_room = (1 << 16) * 4 if (_CONV_DEBUG_FLAGS & 4096) else 0  # tools/sk_timeline.py: 16 int64 stamps per work-group behind the partials
+        kpart = torch.zeros(plan.workspace // 4 + stamp_room, dtype=torch.float32, device=x.device) if stamp_room else \
+            torch.empty(plan.workspace // 4, dtype=torch.float32, device=x.device)  # stream-ordered scratch: freed on return
+        d.kpartial = kpart.data_ptr()
+    if plan.recipe_at == "slices":  # (after the workspace: the planner of the library looks at the split)
+        _recipe_into_descriptor(d, pre)
+    if _CONV_TIMELINE_BUFFER is not None and kpart is None:
+        d.kpartial = _CONV_TIMELINE_BUFFER.data_ptr()  # ksplit stays 0: the kernel only stamps into it (debug_flags bit 12)
+    if f.want_stats:  # the fast kernels fuse the output statistics into their epilogue (else: one stand-alone pass when a consumer asks); attached last:
+        _attach_conv_stats(d, out, g.n, g.cout)  # gm_conv_stats_slots depends on the configuration and the split
+    def launch():
+        check(lib().gm_conv_forward(C.byref(d), _stream()), "gm_conv_forward")
+    if _PROFILE is None:
+        launch()
+    else:
+        nvo, scin, kcin = g.n * math.prod(g.out_sp), sum(f.skip_cin or ()), g.cin * math.prod(g.k)
+        meta = dict(flops=2.0 * nvo * g.cout * (kcin + scin),
+                    bytes=float(g.es * (g.rows * g.cin + nvo * (g.cout * (2 if f.res else 1) + scin) + g.cout * (kcin + scin))),
+                    shape=f"{g.cin}->{g.cout} k{g.k} s{g.conv_stride} out{tuple(g.out_sp)} mode{d.in_mode}")
+        _timed(f"conv_igemm<{str(x.dtype).split('.')[-1]},cfg{d.cfg}{'' if d.ksplit <= 1 else 'k'}>", meta, launch)
+    if d.stats:
+        out._gm_cstats = _compact_stats(out._gm_cstats)
+    if kpart is not None and (_CONV_DEBUG_FLAGS & 4096):
+        _SK_STAMPS = kpart[kpart.numel() - (1 << 18):].view(torch.int64).reshape(-1, 16).clone()
+    return out
 
 
 def conv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], *, kernel, stride=1, padding=0, dilation=1,
@@ -1044,401 +1433,74 @@ def conv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], *,
     if isinstance(x, VirtualCat):
         x, x2 = x.parts
     require_device(x, x2, weight, bias, rowvec, res, out)
-    nsp = x.dim() - 2
-    if nsp < 1 or nsp > 3:
-        raise ValueError("conv expects (N, *spatial, C) with 1-3 spatial axes")
+    g = _conv_geometry(x, x2, weight, packed, cout, kernel, stride, padding, pad_hi, dilation, upsample, transposed, output_padding)
+    dtype, x_ld = x.dtype, arena_ld(x)
+    pending = isinstance(pre, GnRecipe) and pre._done is None
+    f = ConvFacts._make((x2 is not None, x.shape[-1], x_ld, x_ld % g.vecw == 0 and x.data_ptr() % 16 == 0, 0 if weight is None else weight.dim(),
+                         weight is not None and not transposed and weight.shape[2:] == (3, 3, 3), packed is not None,
+                         None if pre is None else ("recipe" if pending else "tables"),
+                         (pre.n, tuple(pre.cs), pre.groups, tuple(st.shape[0] for st in pre.stats)) if pending else None, pre_act, post_act,
+                         rowvec is not None, res is not None, vt is not None, want_stats, None if skip is None else tuple(t.shape[-1] for t in skip[0]),
+                         force_cfg, ksplit, allow_subpixel, pre is not None and fuse_gn_prologue(x)))
 
-    def two_pass():
-        """The operand as ONE activated tensor (gm_gn_apply per part into channel slices / a channel copy), then the plain convolution:
-        the form every kernel covers."""
-        parts = [x] if x2 is None else [x, x2]
-        if pre is None and x2 is None:
-            raise AssertionError
-        xa = torch.empty((*x.shape[:-1], sum(t.shape[-1] for t in parts)), dtype=x.dtype, device=x.device)
-        off = 0
+    def panel():  # the generic MFMA panel, packed on first use: the sub-pixel routes bring their own images (no wasted pack per step)
+        return packed if packed is not None else packed_conv_weight(weight, dtype, transposed)
+    # the order of the routes is part of the behaviour; a route that finds the call not covered after all falls THROUGH to the next
+    if _takes_small_rows(g, f):
+        return _launch_small_rows(g, f, x, panel, bias, pre_act, res, post_act, out)
+    if _takes_edge_2d(g, f):
+        return _launch_edge_2d(x, weight, bias, rowvec, res, post_act, out, want_stats)
+    if _takes_token_gemm(g, f):
+        out, launched = _launch_token_gemm(g, f, x, panel, bias, pre, pre_act, res, post_act, out, vt)
+        if launched:
+            return out
+    if _takes_subpixel_upsample(g, f):
+        got = _conv_subpixel(x, weight, bias, rowvec, res, post_act, out, want_stats, g.n, g.cin, g.cout, g.src)
+        if got is not None:
+            return got
+    if _takes_transposed_subpixel(g, f):
+        got = _conv_subpixel(x, weight, bias, rowvec, res, post_act, out, want_stats, g.n, g.cin, g.cout, g.src,
+                             packed=packed_stride2_dgrad_weight(weight, dtype, g.plo[0]), label=f"transposed k{g.k[0]} s2 as 8 sub-pixel 2x2x2 convolutions")
+        if got is not None:
+            return got
+    if transposed and upsample:
+        raise ValueError("upsample and transposed are exclusive")
+    if min(g.out_sp) <= 0:
+        raise ValueError(f"convolution output would be empty: {g.out_sp}")
+    out, out_ld = _out_and_res((g.n, *g.out_sp[3 - g.nsp:], g.cout), dtype, x.device, out, res)
+    d, keep = _tile_descriptor(g, f, x, x2, panel(), bias, pre, pre_act, rowvec, res, post_act, out, out_ld, skip)
+    plan = _plan_tile_kernels(d, g, f)
+    if plan.recipe_at == "launch":
+        _finalise_into(d, pre)
+    if plan.fallback is None:
+        return _run_tile_kernel(d, g, f, plan, x, weight, pre, out)
+
+    def again(xin, **kw):  # the same convolution once more, on an operand the kernels cover (the panel is packed: handed over as it is)
+        return conv(xin, weight, bias, kernel=kernel, stride=stride, padding=padding, dilation=dilation, pad_hi=pad_hi, upsample=upsample, transposed=transposed,
+                    output_padding=output_padding, rowvec=rowvec, post_act=post_act, out=out, packed=keep[0], cout=g.cout, force_cfg=force_cfg,
+                    want_stats=want_stats, **kw)
+    if plan.fallback == "shortcut_first":
+        # the shortcut as 1x1 launches over the parts first, added as the residual (`res` is None: the shortcut IS the residual)
+        parts, sw, sb = skip
+        acc_t, off = None, 0
         for t in parts:
             c_t = t.shape[-1]
-            if pre is not None:
-                gn_apply(t, pre[0][:, off:off + c_t], pre[1][:, off:off + c_t], pre_act, out=xa[..., off:off + c_t])
-            else:
-                copy_channels(t, xa[..., off:off + c_t])
+            acc_t = conv(t, sw, sb if acc_t is None else None, kernel=1, packed=packed_conv_weight(sw, dtype, cin_range=(off, off + c_t)), cout=g.cout, res=acc_t)
             off += c_t
-        return conv(xa, weight, bias, kernel=kernel, stride=stride, padding=padding, dilation=dilation, pad_hi=pad_hi, upsample=upsample,
-                    transposed=transposed, output_padding=output_padding, rowvec=rowvec, res=res, post_act=post_act, out=out, packed=packed,
-                    cout=cout, force_cfg=force_cfg, want_stats=want_stats, skip=skip, allow_subpixel=allow_subpixel, ksplit=ksplit, vt=vt)
-
-    def tup(v):
-        v = tuple(v) if isinstance(v, (tuple, list)) else (int(v),) * nsp
-        if len(v) != nsp:
-            raise ValueError("per-axis argument has the wrong length")
-        return v
-
-    def pad3(v, fill):
-        return (fill,) * (3 - nsp) + tuple(v)
-
-    k = pad3(tup(kernel), 1)
-    s = pad3(tup(stride), 1)
-    plo = pad3(tup(padding), 0)
-    phi = pad3(tup(pad_hi if pad_hi is not None else padding), 0)
-    dil = pad3(tup(dilation), 1)
-    opad = pad3(tup(output_padding), 0)
-    n, cin = x.shape[0], x.shape[-1] + (0 if x2 is None else x2.shape[-1])
-    src = pad3(tuple(x.shape[1:-1]), 1)
-    dtype = x.dtype
-    if x2 is not None and (x2.shape[:-1] != x.shape[:-1] or x2.dtype != dtype):
-        raise ValueError("the two parts of a concatenated input must agree outside the channel dim")
-    if packed is None:
-        cout = weight.shape[1] if transposed else weight.shape[0]
-        wcin = weight.shape[0] if transposed else weight.shape[1]
-        if wcin != cin:
-            raise ValueError(f"input has {cin} channels but the weight expects {wcin}")
-
-    def panel():  # the generic MFMA panel, packed on first use: the sub-pixel paths below bring their own images (ADVICE r2: no wasted pack per step)
-        return packed if packed is not None else packed_conv_weight(weight, dtype, transposed)
-    rows = n * math.prod(src)
-    vecw = 16 // x.element_size()
-    if (rows <= SMALL_LINEAR_ROWS and x2 is None and k == (1, 1, 1) and s == (1, 1, 1) and not transposed and not upsample and pre is None
-            and rowvec is None and not want_stats and skip is None and force_cfg is None and cin % vecw == 0
-            and arena_ld(x) % vecw == 0 and x.data_ptr() % 16 == 0 and plo == (0, 0, 0) and phi == (0, 0, 0)):
-        # a handful of rows (decode steps, the timestep MLP): the barrier-free small-row GEMM instead of the tiled kernel
-        out_shape = (*x.shape[:-1], cout)
-        if out is None:
-            out = torch.empty(out_shape, dtype=dtype, device=x.device)
-        elif tuple(out.shape) != out_shape or out.dtype != dtype:
-            raise ValueError(f"out has shape {tuple(out.shape)}, expected {out_shape}")
-        if res is not None and (tuple(res.shape) != out_shape or res.dtype != dtype):
-            raise ValueError(f"residual has shape {tuple(res.shape)} / {res.dtype}, expected {out_shape} / {dtype}")
-        b32 = as_f32(bias) if bias is not None else None
-        _timed(f"linear_rows<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(x.element_size() * cin * cout), shape=f"{rows}x{cin}->{cout}"),
-               lambda: check(lib().gm_linear_rows(x.data_ptr(), arena_ld(x), panel().data_ptr(), _ptr(b32), _ptr(res), 0 if res is None else arena_ld(res),
-                                                  out.data_ptr(), arena_ld(out), rows, cin, cout, ACT[pre_act], POST_ACT[post_act], dt_code(dtype),
-                                                  _stream()), "gm_linear_rows"))
-        return out
-    if (EDGE_2D_AS_3D and nsp == 2 and x2 is None and packed is None and weight is not None and weight.dim() == 4 and not transposed and not upsample
-            and cin <= 4 and k == (1, 3, 3) and s == (1, 1, 1) and dil == (1, 1, 1) and plo == (0, 1, 1) and phi == (0, 1, 1) and pre is None
-            and pre_act == "none" and skip is None and force_cfg is None and ksplit is None and cout % vecw == 0 and rows >= DMA_CONV_MIN_VOXELS):
-        # conv_in of a 2-D network (C_in <= 4): the taps x inputs ARE the GEMM K of the edge kernel (cfg 12, conv_edge.hip) -- handed over as the depth-1 volume
-        # it is, the 3x3 kernel as the centre plane of a 3x3x3 one (zero planes in front of and behind it meet the padding planes only)
-        def embed():
-            w5 = torch.zeros((weight.shape[0], weight.shape[1], 3, 3, 3), dtype=weight.dtype, device=weight.device)
-            w5[:, :, 1] = weight.detach()
-            return w5
-        got = conv(x.unsqueeze(1), _cached(weight, ("centre_plane_3d",), embed), bias, kernel=3, padding=1, rowvec=rowvec,
-                   res=None if res is None else res.unsqueeze(1), post_act=post_act, out=None if out is None else out.unsqueeze(1), want_stats=want_stats)
-        y = out if out is not None else got.squeeze(1)
-        st = getattr(got, "_gm_cstats", None)
-        if st is not None:
-            y._gm_cstats = st
-        return y
-    if (TOKEN_GEMM and SMALL_LINEAR_ROWS < rows <= TOKEN_GEMM_MAX_ROWS and cin <= TOKEN_GEMM_MAX_CIN and 2.0 * rows * cin * cout <= TOKEN_GEMM_MAX_FLOP
-            and x2 is None and k == (1, 1, 1) and s == (1, 1, 1) and not upsample and rowvec is None and not want_stats and skip is None
-            and force_cfg is None and ksplit is None and cin % vecw == 0 and arena_ld(x) % vecw == 0 and x.data_ptr() % 16 == 0
-            and plo == (0, 0, 0) and phi == (0, 0, 0) and opad == (0, 0, 0)):
-        out_shape = (*x.shape[:-1], cout)
-        if out is None:
-            out = torch.empty(out_shape, dtype=dtype, device=x.device)
-        elif tuple(out.shape) != out_shape or out.dtype != dtype:
-            raise ValueError(f"out has shape {tuple(out.shape)}, expected {out_shape}")
-        if res is not None and (tuple(res.shape) != out_shape or res.dtype != dtype):
-            raise ValueError(f"residual has shape {tuple(res.shape)} / {res.dtype}, expected {out_shape} / {dtype}")
-        b32 = as_f32(bias) if bias is not None else None
-        if GN_IN_TOKEN_GEMM and isinstance(pre, GnRecipe) and pre._done is None and not transposed:
-            # the GroupNorm is still a recipe (short statistic tables): the wide token GEMM finalises it in its prologue -- no launch for the norm
-            l_tok = rows // n
-            want_vt = (vt is not None and res is None and post_act == "none" and dtype == torch.bfloat16 and l_tok % 64 == 0)
-            if (pre.n == n and sum(pre.cs) == cin and cin <= 384 and cin % (64 // x.element_size()) == 0 and cout >= 32 and l_tok % 64 == 0
-                    and cin % pre.groups == 0 and all(st.shape[0] <= GN_IN_CONSUMER_MAX_ROWS for st in pre.stats) and (vt is None or want_vt)):
-                g = GmGnTables()
-                for i, st in enumerate(pre.stats):
-                    g.stats[i], g.S[i], g.C[i] = st.data_ptr(), st.shape[0], pre.cs[i]
-                g.gamma, g.beta, g.eps, g.groups = _ptr(pre.gamma), _ptr(pre.beta), pre.eps, pre.groups
-                vws, vt_c0, vt_dh = vt if want_vt else (None, 0, 0)
-                _timed(f"token_gemm<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(x.element_size() * (rows * (cin + cout) + cin * cout)),
-                                                                      shape=f"{rows}x{cin}->{cout} (GroupNorm from statistics{' +V^T image' if want_vt else ''})"),
-                       lambda: check(lib().gm_linear_rows_gn(x.data_ptr(), arena_ld(x), C.byref(g), n, l_tok, panel().data_ptr(), _ptr(b32), _ptr(res),
-                                                             0 if res is None else arena_ld(res), out.data_ptr(), arena_ld(out), rows, cin, cout, ACT[pre_act],
-                                                             POST_ACT[post_act], None if vws is None else vws.data_ptr(), int(vt_c0), int(vt_dh), dt_code(dtype),
-                                                             _stream()), "gm_linear_rows_gn"))
-                if want_vt:
-                    out._gm_vt_packed = True
-                return out
-        sc = sh = None
+        return again(x, pre=pre, pre_act=pre_act, res=acc_t)
+    # "two_pass": the operand as ONE activated tensor (gm_gn_apply per part into channel slices / a channel copy), then the plain convolution: the form every
+    # kernel covers
+    parts = [x] if x2 is None else [x, x2]
+    xa = torch.empty((*x.shape[:-1], g.cin), dtype=dtype, device=x.device)
+    off = 0
+    for t in parts:
+        c_t = t.shape[-1]
         if pre is not None:
-            sc, sh = pre
-            if sc.dtype != torch.float32 or sh.dtype != torch.float32 or sc.shape != (n, cin) or sh.shape != (n, cin) or sc.stride(-1) != 1 or sh.stride(-1) != 1 \
-                    or sc.stride(0) != sh.stride(0):
-                raise ValueError("pre = (scale, shift): fp32 [N, Cin] tables with a common row pitch")
-        if (vt is not None and res is None and post_act == "none" and dtype == torch.bfloat16 and (rows // n) % 64 == 0
-                and (sc is None or (sc.stride(0) % 4 == 0 and sc.data_ptr() % 16 == 0 and sh.data_ptr() % 16 == 0))):
-            # vt = (workspace, first V channel, head dim): the stacked q | k | v projection of an attention block also stores the transposed V image
-            # of the LDS-DMA attention kernel (one pack launch less per block); the caller finds `_gm_vt_packed` on the result
-            vws, vt_c0, vt_dh = vt
-            _timed(f"token_gemm<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(x.element_size() * (rows * (cin + cout) + cin * cout)),
-                                                                  shape=f"{rows}x{cin}->{cout} (+V^T image)"),
-                   lambda: check(lib().gm_linear_rows_affine_vt(x.data_ptr(), arena_ld(x), _ptr(sc), _ptr(sh), 0 if sc is None else sc.stride(0), rows // n,
-                                                                panel().data_ptr(), _ptr(b32), out.data_ptr(), arena_ld(out), rows, cin, cout, ACT[pre_act],
-                                                                vws.data_ptr(), int(vt_c0), int(vt_dh), dt_code(dtype), _stream()), "gm_linear_rows_affine_vt"))
-            out._gm_vt_packed = True
-            return out
-        if sc is None or (sc.stride(0) % 4 == 0 and sc.data_ptr() % 16 == 0 and sh.data_ptr() % 16 == 0):
-            _timed(f"token_gemm<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(x.element_size() * (rows * (cin + cout) + cin * cout)),
-                                                                  shape=f"{rows}x{cin}->{cout}"),
-                   lambda: check(lib().gm_linear_rows_affine(x.data_ptr(), arena_ld(x), _ptr(sc), _ptr(sh), 0 if sc is None else sc.stride(0), rows // n,
-                                                             panel().data_ptr(), _ptr(b32), _ptr(res), 0 if res is None else arena_ld(res), out.data_ptr(),
-                                                             arena_ld(out), rows, cin, cout, ACT[pre_act], POST_ACT[post_act], dt_code(dtype), _stream()),
-                                 "gm_linear_rows_affine"))
-            return out
-    if (upsample and x2 is None and SUBPIXEL_UPSAMPLE and allow_subpixel and nsp == 3 and k == (3, 3, 3) and s == (1, 1, 1) and plo == (1, 1, 1) and phi == (1, 1, 1)
-            and dil == (1, 1, 1) and pre is None and pre_act == "none" and skip is None and force_cfg is None and weight is not None
-            and cin % (64 // x.element_size()) == 0 and cout % vecw == 0 and arena_ld(x) % vecw == 0 and x.data_ptr() % 16 == 0
-            and math.prod(src) * n >= DMA_CONV_MIN_VOXELS):
-        got = _conv_subpixel(x, weight, bias, rowvec, res, post_act, out, want_stats, n, cin, cout, src)
-        if got is not None:
-            return got
-    if (transposed and TRANSPOSED_S2_SUBPIXEL and x2 is None and nsp == 3 and s == (2, 2, 2) and k in ((3, 3, 3), (4, 4, 4)) and dil == (1, 1, 1)
-            and plo[0] == plo[1] == plo[2] and stride2_subpixel_covers(k[0], plo[0]) and pre is None and pre_act == "none" and skip is None and force_cfg is None
-            and weight is not None and all((src[i] - 1) * 2 - plo[i] - phi[i] + k[i] + opad[i] == 2 * src[i] for i in range(3))
-            and cin % (64 // x.element_size()) == 0 and cout % vecw == 0 and arena_ld(x) % vecw == 0 and x.data_ptr() % 16 == 0
-            and math.prod(src) * n >= DMA_CONV_MIN_VOXELS):
-        # nn.ConvTranspose3d(stride 2) whose output is exactly twice the input (VQ-VAE up-sampling k = 4 / pad 1, the AutoencoderKL's optional
-        # ConvTranspose k = 3 / pad 1 / output_padding 1, the data gradient of the Downsample convolutions): 8 sub-pixel 2x2x2 convolutions,
-        # one launch of configuration 17 -- no zero-inserted operand, no gather
-        got = _conv_subpixel(x, weight, bias, rowvec, res, post_act, out, want_stats, n, cin, cout, src,
-                             packed=packed_stride2_dgrad_weight(weight, dtype, plo[0]),
-                             label=f"transposed k{k[0]} s2 as 8 sub-pixel 2x2x2 convolutions")
-        if got is not None:
-            return got
-    d = GmConvDesc()
-    d.in_mode, d.fd, d.fh, d.fw = 0, 1, 1, 1
-    act_axes = (0,) * (3 - nsp) + (1,) * nsp
-    if transposed:
-        if upsample:
-            raise ValueError("upsample and transposed are exclusive")
-        d.in_mode = 2
-        d.fd, d.fh, d.fw = s
-        if s == (1, 1, 1):
-            d.in_mode = 0  # no zero insertion: a plain convolution with the flipped, in/out-swapped panel (every fast kernel applies --
-            # this is the data gradient of the stride-1 convolutions)
-        out_sp = tuple((src[i] - 1) * s[i] - plo[i] - phi[i] + dil[i] * (k[i] - 1) + opad[i] + 1 for i in range(3))
-        conv_pad = tuple(dil[i] * (k[i] - 1) - plo[i] for i in range(3))
-        conv_stride = (1, 1, 1)
-    else:
-        virt = src
-        if upsample:
-            d.in_mode = 1
-            d.fd, d.fh, d.fw = tuple(2 if a else 1 for a in act_axes)
-            virt = tuple(src[i] * (2 if act_axes[i] else 1) for i in range(3))
-        out_sp = tuple((virt[i] + plo[i] + phi[i] - dil[i] * (k[i] - 1) - 1) // s[i] + 1 for i in range(3))
-        conv_pad, conv_stride = plo, s
-    if min(out_sp) <= 0:
-        raise ValueError(f"convolution output would be empty: {out_sp}")
-    out_shape = (n, *out_sp[3 - nsp:], cout)
-    if out is None:
-        out = torch.empty(out_shape, dtype=dtype, device=x.device)
-    elif tuple(out.shape) != out_shape or out.dtype != dtype:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {out_shape}")
-    d.x, d.x_ld = x.data_ptr(), arena_ld(x)
-    if x2 is not None:
-        d.x2, d.x2_ld, d.cin_split = x2.data_ptr(), arena_ld(x2), x.shape[-1]
-    packed = panel()
-    d.w = packed.data_ptr()
-    b32 = as_f32(bias) if bias is not None else None
-    d.bias = _ptr(b32)
-    recipe = None
-    if isinstance(pre, GnRecipe) and pre._done is None and NARROW_N and sum(pre.cs) == cin and pre.n == n and k[-2:] == (3, 3) and s == (1, 1, 1) and not transposed \
-            and not upsample and (x2 is None or pre.cs[0] == x.shape[-1]):
-        # a GroupNorm whose finalisation has not run: cfg 24 / 25 can do it in their prologue.  The configuration is chosen as if (scale, shift) existed (a
-        # readable, aligned stand-in); the tables go into the descriptor once it is 24 / 25, anything else materialises them (below)
-        recipe = pre
-        d.pre_scale = d.pre_shift = pre.stats[0].data_ptr()
-    elif pre is not None:
-        sc, sh = pre
-        require_device(sc, sh)
-        if tuple(sc.shape) != (n, cin) or sc.dtype != torch.float32:
-            raise ValueError("pre scale/shift must be fp32 [N, Cin]")
-        d.pre_scale, d.pre_shift = sc.data_ptr(), sh.data_ptr()
-    else:
-        d.pre_scale = d.pre_shift = None
-    if rowvec is not None:
-        if rowvec.dtype != torch.float32 or rowvec.dim() != 2 or rowvec.shape[1] != cout or rowvec.shape[0] not in (1, n):
-            raise ValueError(f"rowvec must be fp32 [1 or N, Cout], got {tuple(rowvec.shape)} {rowvec.dtype}")
-        if rowvec.stride(1) != 1:
-            raise ValueError("rowvec must have unit stride on its last dim")
-        d.rowvec = rowvec.data_ptr()
-        d.rowvec_bstride = 0 if rowvec.shape[0] == 1 else rowvec.stride(0)
-    else:
-        d.rowvec, d.rowvec_bstride = None, 0
-    if res is not None:
-        if tuple(res.shape) != out_shape or res.dtype != dtype:
-            raise ValueError(f"residual has shape {tuple(res.shape)} / {res.dtype}, expected {out_shape} / {dtype}")
-        d.res, d.res_ld = res.data_ptr(), arena_ld(res)
-    else:
-        d.res, d.res_ld = None, 0
-    d.y, d.y_ld = out.data_ptr(), arena_ld(out)
-    d.skip_w = d.skip_bias = None
-    d.skip_x[0] = d.skip_x[1] = None
-    skip_keep = None
-    if skip is not None:
-        parts, sw, sb = skip
-        parts = list(parts)
-        require_device(sw, sb, *parts)
-        if res is not None:
-            raise ValueError("skip and res are exclusive (the shortcut IS the residual)")
-        if not 1 <= len(parts) <= 2 or sw.shape[0] != cout or sw.shape[1] != sum(t.shape[-1] for t in parts) or math.prod(sw.shape[2:]) != 1:
-            raise ValueError("skip = (1 or 2 parts, [Cout, sum(C_part), 1...] weight, bias)")
-        for i, t in enumerate(parts):
-            if tuple(t.shape[:-1]) != out_shape[:-1] or t.dtype != dtype:
-                raise ValueError("skip parts must have the output geometry and dtype")
-            d.skip_x[i], d.skip_ld[i], d.skip_cin[i] = t.data_ptr(), arena_ld(t), t.shape[-1]
-        skip_keep = (packed_conv_weight(sw, dtype), as_f32(sb) if sb is not None else None)
-        d.skip_w, d.skip_bias = skip_keep[0].data_ptr(), _ptr(skip_keep[1])
-    d.N, d.Cin, d.Cout = n, cin, cout
-    d.Ds, d.Hs, d.Ws = src
-    d.Do, d.Ho, d.Wo = out_sp
-    d.kd, d.kh, d.kw = k
-    d.sd, d.sh, d.sw = conv_stride
-    d.pd, d.ph, d.pw = conv_pad
-    d.dd, d.dh, d.dw = dil
-    d.pre_act, d.post_act, d.dtype = ACT[pre_act], POST_ACT[post_act], dt_code(dtype)
-    d.debug_flags = _CONV_DEBUG_FLAGS
-    nvox = math.prod(out_sp)
-    # ---- which kernel, and how the prologue is applied ------------------------------------------------------------------------------
-    # (1) an LDS-DMA configuration when it covers the geometry: fused shortcut, in-LDS prologue, both parts of a VirtualCat read in place;
-    # (2) else the operand is first reduced to ONE activated tensor where needed (two_pass: gn_apply passes, 1x1 shortcut launches), and
-    # (3) the register-staged / generic kernels take what is left, with their own fused prologue for small tensors.
-    dma_ok = False
-    fuse_in_lds = pre is None or DMA_FUSED_PROLOGUE in (True, "always", "1") or (
-        DMA_FUSED_PROLOGUE == "auto" and 2.0 * n * nvox * cout * cin * math.prod(k) <= DMA_FUSED_PROLOGUE_MAX_FLOP)
-    if force_cfg is not None and force_cfg in DMA_CFGS or (force_cfg is None and DMA_CONV and cout > 16 and nvox * n >= DMA_CONV_MIN_VOXELS
-                                                            and fuse_in_lds):
-        try:
-            _choose_conv_cfg(d, nvox, force_cfg, only=DMA_CFGS)
-            dma_ok = True
-        except ValueError:
-            dma_ok = False
-    if NARROW_N and force_cfg is None and ksplit is None and DMA_CONV and fuse_in_lds and nvox * n >= DMA_CONV_MIN_VOXELS:
-        bk = 64 // x.element_size()
-        if dma_ok and d.cfg == 11 and SPLITK:
-            tiles = n * ((out_sp[0] + 3) // 4) * ((out_sp[1] + 3) // 4) * ((out_sp[2] + 15) // 16) * ((cout + 63) // 64)
-            deep = cin // bk + (0 if skip is None else sum(t.shape[-1] for t in skip[0]) // bk)
-            if tiles < SPLITK_MAX_TILES and min(cin // bk, SPLITK_MAX, SPLITK_TARGET_WGS // tiles) > 1 and deep <= NARROW_N_MAX_CHUNKS:
-                try:  # the launch would be split over K: K-complete on 16-channel blocks instead (cfg 24)
-                    _choose_conv_cfg(d, nvox, 24, only=DMA_CFGS)
-                except ValueError:
-                    _choose_conv_cfg(d, nvox, 11, only=DMA_CFGS)
-        elif not dma_ok and cout <= 16 and (d.kd == 3 or NARROW_N_2D) and 2.0 * n * nvox * cout * cin * math.prod(k) <= NARROW_HEAD_MAX_FLOP:
-            # a narrow output head of a SMALL problem (the latent UNet's 64 -> 4, the 2-D UNet's 32 -> 1): the generic tile kernel otherwise (42 us at 32^3); the
-            # C_out = 1 head of a large volume keeps its depth-marching kernel (cfg 20)
-            try:
-                _choose_conv_cfg(d, nvox, 24 if d.kd == 3 else 25, only=DMA_CFGS)
-                dma_ok = True
-            except ValueError:
-                pass
-    def recipe_into_descriptor():
-        """The pending GroupNorm as statistic tables in the descriptor; False (descriptor restored) when the kernel does not take that form after all."""
-        keep = (d.pre_scale, d.pre_shift)
-        d.pre_scale = d.pre_shift = None
-        for i, st in enumerate(recipe.stats):
-            d.pre_stats[i], d.pre_S[i], d.pre_C[i] = st.data_ptr(), st.shape[0], recipe.cs[i]
-        d.pre_gamma, d.pre_beta, d.pre_eps, d.pre_groups = _ptr(recipe.gamma), _ptr(recipe.beta), recipe.eps, recipe.groups
-        if lib().gm_conv_lds_bytes(C.byref(d)) > 0:
-            return True
-        d.pre_stats[0] = d.pre_stats[1] = None  # (a table longer than the short form's bound, more channels than the LDS tables hold)
-        d.pre_S[0] = d.pre_S[1] = d.pre_C[0] = d.pre_C[1] = 0
-        d.pre_scale, d.pre_shift = keep
-        return False
-
-    recipe_pending_split = False
-    if recipe is not None:
-        if dma_ok and d.cfg in (24, 25):
-            if not recipe_into_descriptor():
-                recipe = None
-        elif dma_ok and d.cfg == 11 and GN_IN_SPLIT_SLICES and (ksplit is not None or SPLITK):
-            recipe_pending_split = True  # decided with the split (below): the K slices of conv_sk.hip finalise the norm themselves
+            gn_apply(t, pre[0][:, off:off + c_t], pre[1][:, off:off + c_t], pre_act, out=xa[..., off:off + c_t])
         else:
-            recipe = None
-        if recipe is None:
-            sc, sh = pre.materialise()
-            d.pre_scale, d.pre_shift = sc.data_ptr(), sh.data_ptr()
-    if not dma_ok:
-        if force_cfg is not None and force_cfg in DMA_CFGS:
-            raise ValueError(f"configuration {force_cfg} does not cover this convolution")
-        if x2 is not None:
-            return two_pass()  # only the LDS-DMA kernels read a concatenated input in place
-        # (round 5: NOT the large 1x1 projections -- the q | k | v projection of C2's mid-block attention, 32 768 x 256 -> 768, is 102 us fused against
-        #  62 + 12 two-pass in isolation, and 0.109 against 0.081 + 0.035 inside the forward: nothing, profiles/r05_qkv_projection_c2.txt)
-        if pre is not None and force_cfg is None and cout > 16 and math.prod(k) > 1 and not fuse_gn_prologue(x):
-            return two_pass()  # a large ResnetBlock convolution: the HBM-bound gm_gn_apply pass + the prologue-free kernel (which still fuses
-            # the shortcut) beats both the in-LDS and the register-staged prologue (GN_APPLY_POLICY, DMA_FUSED_PROLOGUE)
-        if skip is not None:
-            # the shortcut as 1x1 launches over the parts first, added as the residual (`res` is None: the shortcut IS the residual)
-            parts, sw, sb = skip
-            parts = list(parts)
-            acc_t, off = None, 0
-            for t in parts:
-                c_t = t.shape[-1]
-                acc_t = conv(t, sw, sb if acc_t is None else None, kernel=1,
-                             packed=packed_conv_weight(sw, dtype, cin_range=(off, off + c_t)), cout=cout, res=acc_t)
-                off += c_t
-            return conv(x, weight, bias, kernel=kernel, stride=stride, padding=padding, dilation=dilation, pad_hi=pad_hi,
-                        upsample=upsample, transposed=transposed, output_padding=output_padding, pre=pre, pre_act=pre_act,
-                        rowvec=rowvec, res=acc_t, post_act=post_act, out=out, packed=packed, cout=cout, force_cfg=force_cfg,
-                        want_stats=want_stats)
-        no_cin = (12,) if (weight is None or transposed or tuple(weight.shape[2:]) != (3, 3, 3)) else ()  # (cfg 12 derives its image from the weight)
-        _choose_conv_cfg(d, nvox, force_cfg, exclude=(DMA_CFGS + no_cin) if force_cfg is None else ())
-    if d.cfg == 12:  # configuration 12 reads its weight fragments from the K-major image
-        if weight is None or transposed or tuple(weight.shape[2:]) != (3, 3, 3):
-            raise ValueError("configuration 12 needs the original [Cout, Cin, 3, 3, 3] weight (its K-major image is derived from it)")
-        cin_keep = packed_cin_weight(weight, dtype)
-        d.w = cin_keep.data_ptr()
-    kpart = None
-    if dma_ok and d.cfg == 11 and (ksplit is not None or SPLITK):
-        nchunks = cin // (64 // x.element_size())
-        tiles = n * ((out_sp[0] + 3) // 4) * ((out_sp[1] + 3) // 4) * ((out_sp[2] + 15) // 16) * ((cout + 63) // 64)
-        ks = ksplit if ksplit is not None else (min(nchunks, SPLITK_MAX, SPLITK_TARGET_WGS // tiles) if tiles < SPLITK_MAX_TILES else 1)
-        if ks > 1:
-            ks = -(-nchunks // -(-nchunks // ks))  # ceil(nchunks / chunks per slice): 12 chunks over "8" slices = 6 slices of 2, none empty
-        if ks > 1:
-            if _SK_KERNEL is not None:
-                lib().gm_conv_sk_set_enabled(int(_SK_KERNEL))
-            d.ksplit = int(ks)
-            nbytes = lib().gm_conv_splitk_workspace_bytes(C.byref(d))
-            if nbytes > 0:
-                stamp_room = (1 << 16) * 4 if (_CONV_DEBUG_FLAGS & 4096) else 0  # tools/sk_timeline.py: 16 int64 stamps per work-group behind the partials
-                kpart = torch.zeros(nbytes // 4 + stamp_room, dtype=torch.float32, device=x.device) if stamp_room else \
-                    torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)  # stream-ordered scratch: freed on return
-                d.kpartial = kpart.data_ptr()
-            elif ksplit is not None:
-                raise ValueError(f"split-K by {ks} is not available for this convolution")
-            else:
-                d.ksplit = 0
-    if recipe_pending_split:
-        if not (d.ksplit > 1 and kpart is not None and recipe_into_descriptor()):
-            sc, sh = pre.materialise()
-            d.pre_scale, d.pre_shift = sc.data_ptr(), sh.data_ptr()
-    if _CONV_TIMELINE_BUFFER is not None and kpart is None:
-        d.kpartial = _CONV_TIMELINE_BUFFER.data_ptr()  # ksplit stays 0: the kernel only stamps into it (debug_flags bit 12)
-    d.stats = None
-    if want_stats:  # the fast kernels fuse the output statistics into their epilogue (else: one stand-alone pass when a consumer asks)
-        _attach_conv_stats(d, out, n, cout)
-    if _PROFILE is None:
-        check(lib().gm_conv_forward(C.byref(d), _stream()), "gm_conv_forward")
-    else:
-        es = x.element_size()
-        taps = k[0] * k[1] * k[2]
-        nvo = n * math.prod(out_sp)
-        scin = 0 if skip is None else sum(t.shape[-1] for t in skip[0])
-        meta = dict(flops=2.0 * nvo * cout * (cin * taps + scin),
-                    bytes=float(es * (n * math.prod(src) * cin + nvo * (cout * (2 if res is not None else 1) + scin) + cout * (cin * taps + scin))),
-                    shape=f"{cin}->{cout} k{k} s{conv_stride} out{tuple(out_sp)} mode{d.in_mode}")
-        _timed(f"conv_igemm<{str(dtype).split('.')[-1]},cfg{d.cfg}{'' if d.ksplit <= 1 else 'k'}>", meta,
-               lambda: check(lib().gm_conv_forward(C.byref(d), _stream()), "gm_conv_forward"))
-    if d.stats:
-        out._gm_cstats = _compact_stats(out._gm_cstats)
-    if kpart is not None and (_CONV_DEBUG_FLAGS & 4096):
-        global _SK_STAMPS
-        _SK_STAMPS = kpart[kpart.numel() - (1 << 18):].view(torch.int64).reshape(-1, 16).clone()
-    return out
+            copy_channels(t, xa[..., off:off + c_t])
+        off += c_t
+    return again(xa, res=res, skip=skip, allow_subpixel=allow_subpixel, ksplit=ksplit, vt=vt)
 
 
 def linear(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], **kw) -> torch.Tensor:

@@ -476,6 +476,82 @@ def test_tile_configuration_policy_of_the_lds_dma_convolutions():
         ops.DMA_WIDE_WAVES = keep
 
 
+def test_tile_kernel_plan_without_a_gpu():
+    """ops._plan_tile_kernels on a hand-filled descriptor, the geometry record and operand facts (no tensor, no GPU): the cfg 24 substitution and its depth
+    bound, the slice count of a split launch, where a pending GroupNorm is finalised, the narrow-head rule, both fallbacks, force_cfg inside / outside
+    DMA_CFGS."""
+    from generativemodels_amd import _native as nat
+    from generativemodels_amd import ops
+
+    def plan(size, cin, cout, *, dtype=torch.bfloat16, stride=1, dilation=1, pre=None, cat=False, skip_cin=None, force_cfg=None, ksplit=None, gn_fused=True):
+        x = torch.empty((1, size, size, size, cin), dtype=dtype, device="meta")
+        w = torch.empty((cout, cin, 3, 3, 3), dtype=dtype, device="meta")
+        g = ops._conv_geometry(x, None, w, None, None, 3, stride, dilation, None, dilation, False, False, 0)
+        assert g.out_sp == (size // stride,) * 3 and g.rows == size ** 3 and g.vecw == 16 // g.es
+        f = ops.ConvFacts(cat=cat, cin0=cin // 2 if cat else cin, x_ld=cin, x_vec=True, weight_dim=5, w333=True, packed=False, pre=pre,
+                          recipe=(1, (cin,), 32, (16,)) if pre == "recipe" else None, pre_act="silu" if pre else "none", post_act="none", rowvec=False, res=False,
+                          vt=False, want_stats=False, skip_cin=skip_cin, force_cfg=force_cfg, ksplit=ksplit, allow_subpixel=True, gn_fused=gn_fused)
+        d = nat.GmConvDesc()
+        ops._geometry_into(d, 1, cin, cout, g.src, g.out_sp, g.k, g.conv_stride, g.conv_pad, g.dil, dtype)
+        d.fd = d.fh = d.fw = 1
+        d.x, d.x_ld, d.y, d.y_ld, d.w = 0x1000, cin, 0x2000, cout, 0x3000
+        if cat:
+            d.x2, d.x2_ld, d.cin_split = 0x6000, cin // 2, cin // 2
+        if pre:
+            d.pre_scale, d.pre_shift, d.pre_act = 0x4000, 0x4000 if pre == "recipe" else 0x5000, 1
+        for i, c in enumerate(skip_cin or ()):
+            d.skip_x[i], d.skip_ld[i], d.skip_cin[i], d.skip_w = 0x7000 + 0x1000 * i, c, c, 0x9000
+        return ops._plan_tile_kernels(d, g, f), d
+
+    def chosen(*a, **kw):
+        p, d = plan(*a, **kw)
+        return d.cfg, p.ksplit
+
+    # a launch that would be split over K runs K-complete on cfg 24 up to NARROW_N_MAX_CHUNKS (6) K chunks of 32 bf16 / 16 fp32 channels; deeper ones keep the slices
+    assert chosen(32, 64, 64) == (24, 0) and chosen(16, 192, 64) == (24, 0) and chosen(16, 96, 64, dtype=torch.float32) == (24, 0)
+    assert chosen(16, 256, 256) == (11, 4) and chosen(8, 512, 512) == (11, 8) and chosen(16, 224, 64) == (11, 7)
+    assert chosen(16, 128, 64, skip_cin=(64, 64)) == (11, 4)                                     # the shortcut's chunks count: 4 + 4 deep
+    assert chosen(128, 64, 64) == (14, 0) and chosen(32, 256, 256) == (14, 0)                      # enough tiles: not split, no substitution
+    keep = ops.NARROW_N_MAX_CHUNKS
+    try:
+        ops.NARROW_N_MAX_CHUNKS = 8
+        assert chosen(16, 256, 256) == (24, 0)
+    finally:
+        ops.NARROW_N_MAX_CHUNKS = keep
+    # forced slice counts: no slice stays empty (12 chunks over "8" slices = 6 slices of 2); 1 = not split; the policy is not asked
+    assert chosen(16, 384, 128, ksplit=8) == (11, 6) and chosen(16, 256, 256, ksplit=2) == (11, 2) and chosen(16, 256, 256, ksplit=64) == (11, 8)
+    assert chosen(16, 256, 256, ksplit=1) == (11, 0) and chosen(32, 64, 64, ksplit=2) == (11, 2)
+    p, d = plan(16, 256, 256)
+    assert p.workspace == 4 * 16 ** 3 * 256 * 4 and d.ksplit == 4 and p.fallback is None and p.recipe_at is None
+    with pytest.raises(ValueError, match="split-K by 2 is not available"):
+        plan(16, 256, 4096, dtype=torch.float32, ksplit=2)                                          # more channel vectors per row than the combine kernel has threads
+    assert chosen(16, 256, 4096, dtype=torch.float32) == (11, 0)                                    # ... which the policy turns into an unsplit launch
+    # a pending GroupNorm: the prologue of cfg 24 / 25, the K slices of a split cfg 11 launch, or the finalisation launch
+    assert plan(32, 64, 64, pre="recipe")[0].recipe_at == "descriptor"
+    assert plan(16, 256, 256, pre="recipe")[0].recipe_at == "slices" and plan(16, 256, 256, pre="recipe", ksplit=4)[0].recipe_at == "slices"
+    assert plan(16, 256, 256, pre="recipe", ksplit=1)[0].recipe_at == "launch"                     # cfg 11, not split
+    assert plan(64, 64, 64, pre="recipe", force_cfg=14)[0].recipe_at == "launch"                   # a kernel without the statistics prologue
+    assert plan(32, 64, 64, pre="recipe", stride=2)[0].recipe_at is None and plan(32, 64, 64, pre="tables")[0].recipe_at is None
+    p, _ = plan(128, 64, 64, pre="recipe", gn_fused=False)                                           # above DMA_FUSED_PROLOGUE_MAX_FLOP: the two-pass form
+    assert (p.fallback, p.recipe_at) == ("two_pass", "launch")
+    # the narrow-head rule: small C_out <= 16 problems on cfg 24; the large C_out = 1 head keeps its marching kernel
+    assert chosen(32, 64, 4) == (24, 0) and chosen(128, 64, 1)[0] == 20 and chosen(32, 64, 4, pre="tables") == (24, 0)
+    # fallbacks when no LDS-DMA configuration covers the geometry
+    assert plan(32, 64, 64, dilation=2, cat=True)[0].fallback == "two_pass" and plan(32, 64, 64, dilation=2, skip_cin=(64,))[0].fallback == "shortcut_first"
+    assert plan(32, 64, 64, dilation=2, pre="tables", skip_cin=(64,), gn_fused=False)[0].fallback == "two_pass"   # (the shortcut goes along into the second pass)
+    assert plan(32, 64, 64, dilation=2)[0].fallback is None and chosen(32, 64, 64, dilation=2)[0] not in ops.DMA_CFGS
+    # force_cfg: inside DMA_CFGS it must cover the geometry, outside it goes to the generic chooser
+    assert chosen(32, 64, 64, force_cfg=11) == (11, 2) and chosen(32, 64, 64, force_cfg=24) == (24, 0) and chosen(64, 64, 64, force_cfg=16) == (16, 0)
+    assert chosen(32, 64, 64, force_cfg=4) == (4, 0) and chosen(64, 64, 64, stride=2, force_cfg=15) == (15, 0)
+    for cfg in (15, 25, 17):
+        with pytest.raises(ValueError, match=f"configuration {cfg} does not cover this convolution"):
+            plan(32, 64, 64, force_cfg=cfg)
+    # the two counting rules, each written once
+    assert ops._conv_tiles(1, (16, 16, 16), 256) == 64 and ops._conv_tiles(2, (5, 4, 17), 65) == 2 * 2 * 1 * 2 * 2
+    g16 = ops._conv_geometry(torch.empty((1, 16, 16, 16, 256), device="meta"), None, torch.empty((256, 256, 3, 3, 3), device="meta"), None, None, 3, 1, 1, None, 1, False, False, 0)
+    assert ops._split_slices(g16, 8, None) == 4 and ops._split_slices(g16, 12, 8) == 6 and ops._split_slices(g16, 8, 1) == 1 and ops._split_slices(g16, 3, None) == 3
+
+
 def test_native_planners_accept_and_reject_geometries_without_a_gpu():
     """Host-side planning of the C-ABI library runs without a GPU: tile-configuration eligibility (gm_conv_lds_bytes: > 0 = bytes of LDS,
     -1 = configuration does not cover the geometry) for the LDS-DMA kernels incl. the sub-pixel up-sampling variant, and the weight-gradient
@@ -821,3 +897,373 @@ def test_attention_backward_policy_and_timestep_row_hand_over_host_side():
                             norm_num_groups=32, num_class_embeds=3)
     assert mc.time_rows_table(torch.zeros(4)) is None
     assert DiffusionInferer.BATCHED_TIME_ROWS is True
+
+
+# ---- route census of ops.conv: which native entry points, in which order, with which descriptors -------------------------------------
+# Every case is a dict: cin (int, or (c1, c2) = a VirtualCat), cout, sp (spatial extents) and options read by _run_conv_route_case; whatever
+# it does not know is handed to ops.conv as it is.  The expected records (tests/golden/conv_routes.json.gz: 370 KB of JSON, gzip-compressed) were written by
+# _conv_route_census(write=...) at the commit named in that file, BEFORE ops.conv was split into a planner and launchers.
+def _c(cin, cout, sp, **kw):
+    return dict(cin=cin, cout=cout, sp=tuple(sp) if isinstance(sp, (tuple, list)) else (sp,) * 3, **kw)
+
+
+def _recipe(ops, cs, n, v, rows, groups=32, done=False):
+    stats = [torch.empty((rows, n, c, 2), dtype=torch.float64) for c in cs]
+    c = sum(cs)
+    rec = ops.GnRecipe(stats, list(cs), n, v, groups, 1e-5, torch.ones(c), torch.zeros(c), stats[0].device)
+    if done:
+        rec.materialise()
+    return rec
+
+
+def _run_conv_route_case(case):
+    """-> the list of recorded native calls of one case (a raised exception is recorded as ["raise", type, message])."""
+    import math
+
+    from _util import conv_on_cpu
+    from generativemodels_amd import ops
+    c = dict(case)
+    dt = {"bf16": torch.bfloat16, "fp32": torch.float32}[c.pop("dtype", "bf16")]
+    n, sp, cin, cout = c.pop("n", 1), c.pop("sp"), c.pop("cin"), c.pop("cout")
+    attrs, via_linear = c.pop("attrs", {}), c.pop("linear", False)
+    cs = tuple(cin) if isinstance(cin, tuple) else (cin,)
+    cin, nsp = sum(cs), len(sp)
+
+    def axes(v, fill=None):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v,) * nsp
+    k = axes(c.get("kernel", 3))
+    c.setdefault("kernel", 3)
+    if "padding" not in c:
+        c["padding"] = tuple(c.get("dilation", 1) * (kk // 2) if isinstance(c.get("dilation", 1), int) else kk // 2 for kk in k)
+    s, plo, dil = axes(c.get("stride", 1)), axes(c["padding"]), axes(c.get("dilation", 1))
+    phi, opad = axes(c["pad_hi"] if c.get("pad_hi") is not None else c["padding"]), axes(c.get("output_padding", 0))
+    try:
+        if c.get("transposed"):
+            out_sp = tuple((sp[i] - 1) * s[i] - plo[i] - phi[i] + dil[i] * (k[i] - 1) + opad[i] + 1 for i in range(nsp))
+        else:
+            up = 2 if c.get("upsample") else 1
+            out_sp = tuple((sp[i] * up + plo[i] + phi[i] - dil[i] * (k[i] - 1) - 1) // s[i] + 1 for i in range(nsp))
+    except IndexError:  # a per-axis argument of the wrong length: ops.conv is expected to refuse it
+        out_sp = sp
+    out_sp = tuple(max(v, 1) for v in out_sp)
+    out_shape = (n, *out_sp, cout)
+
+    def arena(shape, dtype=dt, pad=0, off=0):  # (pad, off): a channel slice of a wider tensor -- leading dim shape[-1] + pad, first element `off` in
+        if not pad and not off:
+            return torch.empty(shape, dtype=dtype)
+        return torch.empty((*shape[:-1], shape[-1] + pad), dtype=dtype)[..., off:off + shape[-1]]
+    x_pad, x_off = c.pop("x_view", (0, 0))
+    parts = [arena((n, *sp, ci), pad=x_pad, off=x_off) for ci in cs]
+    cat_mismatch = c.pop("cat_mismatch", False)
+    wshape = ((cin, cout) if c.get("transposed") else (cout, cin)) + k
+    wcin = c.pop("weight_cin", None)
+    if wcin is not None:
+        wshape = (cout, wcin) + k
+    weight = torch.empty(wshape, dtype=c.pop("weight_dtype", dt))
+    bias = torch.empty(cout, dtype=dt) if c.pop("bias", True) else None
+    with conv_on_cpu() as rec, torch.no_grad():
+        keep = {a: getattr(ops, a) for a in attrs}
+        try:
+            for a, v in attrs.items():
+                setattr(ops, a, v)
+            if c.pop("packed", False):
+                c["packed"], c["cout"], weight = torch.empty(cin * cout * math.prod(k), dtype=dt), cout, None
+            pre = c.pop("pre", None)
+            if pre is not None:
+                kind, arg = pre if isinstance(pre, tuple) else (pre, None)
+                if kind == "tuple":  # arg: row pitch of the tables (default: dense), or a dtype name
+                    tdt = torch.float64 if arg == "fp64" else torch.float32
+                    pitch = arg if isinstance(arg, int) else cin
+                    c["pre"] = tuple(torch.empty((n, pitch), dtype=tdt)[:, :cin] for _ in range(2))
+                elif kind == "tuple_bad_shape":
+                    c["pre"] = (torch.empty((n, cin + 1)), torch.empty((n, cin + 1)))
+                else:  # "recipe" / "recipe_done": arg = rows of the statistic tables (or (rows, groups) / (rows, groups, part channels))
+                    arg = arg if isinstance(arg, tuple) else (arg, 32)
+                    c["pre"] = _recipe(ops, arg[2] if len(arg) > 2 else cs, n, math.prod(sp), arg[0], arg[1], done=kind == "recipe_done")
+            rowvec = c.pop("rowvec", None)
+            if rowvec is not None:
+                c["rowvec"] = {"1": lambda: torch.empty((1, cout)), "n": lambda: torch.empty((n, cout)), "bf16": lambda: torch.empty((1, cout), dtype=torch.bfloat16),
+                               "strided": lambda: torch.empty((1, 2 * cout))[:, ::2], "wide": lambda: torch.empty((1, cout + 1))}[rowvec]()
+            for name in ("res", "out"):
+                v = c.pop(name, None)
+                if v is not None:  # True, "pad4" (leading dim cout + 4), "bad" (wrong shape), "f32" (wrong dtype)
+                    c[name] = arena(out_shape if v != "bad" else (n, *out_sp, cout + 1), dtype=torch.float32 if v == "f32" and dt != torch.float32 else
+                                    (torch.bfloat16 if v == "f32" else dt), pad=4 if v == "pad4" else 0)
+            skip = c.pop("skip", None)
+            if skip is not None:  # (part channels...), optionally a dict of deviations
+                dev = skip[-1] if isinstance(skip[-1], dict) else {}
+                scs = [v for v in skip if not isinstance(v, dict)]
+                sparts = [arena((n, *(out_sp if not dev.get("bad_geometry") else tuple(v + 1 for v in out_sp)), sc)) for sc in scs]
+                sw = torch.empty((cout + dev.get("cout_off", 0), sum(scs)) + (1,) * nsp, dtype=dt)
+                c["skip"] = (sparts, sw, torch.empty(cout, dtype=dt) if dev.get("bias", True) else None)
+            if c.pop("vt", False):
+                c["vt"] = (torch.empty((n, cout // 3, math.prod(sp)), dtype=dt), 2 * cout // 3, 64)
+            rec.calls.clear()
+            x = parts[0] if len(parts) == 1 else ops.VirtualCat(parts)
+            if cat_mismatch:  # (the constructor refuses it: a part replaced afterwards)
+                x.parts[1] = x.parts[1].float()
+            if via_linear:  # ops.linear over (rows, C): n must be 1
+                c.pop("kernel"), c.pop("padding")
+                for name in ("res", "out"):
+                    if c.get(name) is not None:
+                        c[name] = c[name].squeeze(0)
+                y = ops.linear(x.squeeze(0), weight.reshape(cout, cin), bias, **c)
+            else:
+                y = ops.conv(x, weight, bias, **c)
+            flags = [a for a in ("_gm_cstats", "_gm_vt_packed") if getattr(y, a, None) is not None]
+            rec.calls.append(["result", list(y.shape), flags, [list(getattr(y, "_gm_cstats").shape)] if "_gm_cstats" in flags else []])
+            if c.get("out") is not None:
+                rec.calls.append(["result is out", y is c["out"] or y.data_ptr() == c["out"].data_ptr()])
+        except Exception as ex:  # noqa: BLE001 -- the census records whatever the call raises
+            rec.calls[:] = [["raise", type(ex).__name__, str(ex)]]  # (instead of whatever was launched before the refusal)
+        finally:
+            for a, v in keep.items():
+                setattr(ops, a, v)
+        return rec.calls
+
+
+def _unet_layer_cases(nsp, size, chans, cin, cout, n=1, dtype="bf16", recipe_rows=None):
+    """The convolutions of a DiffusionModelUNet forward: conv_in, per level two ResnetBlock convolutions and the Downsample, the up path over
+    concatenated inputs with the 1x1 shortcut, the Upsample convolutions, the output head and the time-embedding linears."""
+    cases, r, prev = [], size, chans[0]
+    cases.append(_c(cin, chans[0], (size,) * nsp, n=n, dtype=dtype, want_stats=True))
+    for rows_in, rows_out in ((chans[0], 4 * chans[0]), (4 * chans[0], 4 * chans[0])):
+        cases.append(_c(rows_in, rows_out, (1,), n=n, dtype=dtype, kernel=1, post_act="silu" if rows_in == chans[0] else "none"))
+
+    def pre(cs, res):
+        return ("recipe", (recipe_rows, 32, cs)) if recipe_rows and res <= 32 else "tuple"
+    for lvl, ch in enumerate(chans):
+        sp = (r,) * nsp
+        cases.append(_c(4 * chans[0], ch, (1,), n=n, dtype=dtype, kernel=1, pre_act="silu"))
+        cases.append(_c(prev, ch, sp, n=n, dtype=dtype, pre=pre((prev,), r), pre_act="silu", rowvec="n", want_stats=True))
+        if prev == ch:
+            cases.append(_c(ch, ch, sp, n=n, dtype=dtype, pre=pre((ch,), r), pre_act="silu", res=True, want_stats=True))
+        else:
+            cases.append(_c(ch, ch, sp, n=n, dtype=dtype, pre=pre((ch,), r), pre_act="silu", skip=(prev,), want_stats=True))
+        up_in = (ch, ch if lvl == len(chans) - 1 else chans[min(lvl + 1, len(chans) - 1)])
+        for a, b in {(ch, ch), (ch, prev), up_in}:
+            cases.append(_c((a, b), ch, sp, n=n, dtype=dtype, pre=pre((a, b), r), pre_act="silu", rowvec="n", want_stats=True))
+            cases.append(_c(ch, ch, sp, n=n, dtype=dtype, pre=pre((ch,), r), pre_act="silu", skip=(a, b), want_stats=True))
+        if lvl < len(chans) - 1:
+            cases.append(_c(ch, ch, sp, n=n, dtype=dtype, stride=2, want_stats=True))
+            cases.append(_c(ch, ch, (r // 2,) * nsp, n=n, dtype=dtype, upsample=True, want_stats=True))
+            r //= 2
+        prev = ch
+    cases.append(_c(chans[0], cout, (size,) * nsp, n=n, dtype=dtype, pre=pre((chans[0],), size), pre_act="silu"))
+    return cases
+
+
+def _attention_cases(c, tokens, n=1, dtype="bf16", rows=16):
+    """The 1x1 projections of a spatial attention block over `tokens` rows of c channels: stacked q | k | v (GroupNorm in the prologue, V^T image),
+    and the output projection onto the residual."""
+    return [_c(c, 3 * c, (tokens,), n=n, dtype=dtype, kernel=1, packed=True, pre="tuple", vt=True),
+            _c(c, 3 * c, (tokens,), n=n, dtype=dtype, kernel=1, packed=True, pre=("recipe", rows), vt=True),
+            _c(c, 3 * c, (tokens,), n=n, dtype=dtype, kernel=1, packed=True, pre="tuple"),
+            _c(c, c, (tokens,), n=n, dtype=dtype, kernel=1, res=True)]
+
+
+def _conv_route_cases():
+    S = []
+    # -- the table of the issue: bf16, and the 3-D rows in fp32
+    for dt in ("bf16", "fp32"):
+        S += [_c(64, 64, 128, dtype=dt, want_stats=True), _c(64, 64, 32, dtype=dt), _c(256, 256, 16, dtype=dt), _c(512, 512, 8, dtype=dt), _c(64, 4, 32, dtype=dt),
+              _c(128, 128, 20, dtype=dt, upsample=True, want_stats=True), _c(128, 128, 20, dtype=dt, want_stats=True), _c(64, 64, 64, dtype=dt, stride=2),
+              _c(64, 64, 128, dtype=dt, pre="tuple", pre_act="silu", want_stats=True), _c(64, 64, 32, dtype=dt, pre="tuple", pre_act="silu", want_stats=True),
+              _c((128, 64), 64, 16, dtype=dt, pre=("recipe", 16), pre_act="silu", want_stats=True, rowvec="1", skip=(128, 64)),
+              _c((256, 256), 256, 8, dtype=dt, pre=("recipe", 4), pre_act="silu", want_stats=True, rowvec="1", skip=(256, 256)),
+              _c(64, 1, 128, dtype=dt), _c(64, 64, 32, dtype=dt, dilation=2), _c(64, 64, 32, dtype=dt, force_cfg=15)]
+    S += [_c(1, 32, (64, 64)), _c(32, 32, (64, 64)), _c(64, 192, (1024,), kernel=1), _c(64, 192, (1024,), kernel=1, packed=True, pre=("recipe", 16)),
+          _c((48, 16), 32, (32, 32), kernel=1, bias=False), _c(64, 192, (1024,), kernel=1, pre=("tuple", 67), bias=False)]
+    # -- 1-D and 2-D convolutions, batches
+    S += [_c(64, 64, (1024,)), _c(64, 64, (1024,), dtype="fp32", stride=2), _c(32, 64, (64, 64), n=16, want_stats=True), _c(64, 64, (32, 32), n=16, dtype="fp32", want_stats=True),
+          _c(64, 64, 16, n=2, rowvec="n", want_stats=True), _c(64, 64, 32, n=4, want_stats=True), _c(48, 48, 32), _c(48, 80, (64, 64)), _c(8, 8, 16), _c(64, 12, (64, 64)),
+          _c(96, 96, 64, want_stats=True), _c(24, 24, 32, dtype="fp32"), _c(64, 64, (8, 16, 40)), _c(64, 64, (3, 3, 3)), _c(64, 128, 2, n=2)]
+    # -- small-row GEMM (rows <= 64): with and without res, through ops.linear, the bounds and each operand fact that refuses it
+    for rows in (1, 16, 64, 65):
+        S += [_c(64, 256, (rows,), kernel=1), _c(64, 256, (rows,), kernel=1, res=True, post_act="silu", pre_act="silu")]
+    S += [_c(256, 256, (1,), kernel=1, linear=True), _c(256, 256, (8,), kernel=1, linear=True, res=True, out=True), _c(64, 64, (2, 2, 2), kernel=1, dtype="fp32", out=True),
+          _c(36, 64, (16,), kernel=1), _c(64, 64, (16,), kernel=1, pre="tuple"), _c(64, 64, (16,), kernel=1, rowvec="1"), _c(64, 64, (16,), kernel=1, want_stats=True),
+          _c(64, 64, (16,), kernel=1, x_view=(4, 0)), _c(64, 64, (16,), kernel=1, x_view=(8, 4)), _c(64, 64, (16,), kernel=1, padding=1), _c(64, 64, (16,), kernel=1, stride=2),
+          _c(64, 64, (16,), kernel=1, transposed=True), _c(64, 64, (16,), kernel=1, upsample=True), _c(64, 64, (16,), kernel=1, force_cfg=4), _c(64, 64, (16,), kernel=1, skip=(64,)),
+          _c((32, 32), 64, (16,), kernel=1), _c(64, 64, (16,), kernel=1, out="bad"), _c(64, 64, (16,), kernel=1, res="bad"), _c(64, 64, (16,), kernel=1, res="f32"),
+          _c(64, 64, (16,), kernel=1, packed=True, bias=False)]
+    # -- token GEMM: row / cin / FLOP bounds on both sides, pre as tuple and as recipe, V^T image, the facts that refuse it
+    S += [_c(64, 64, (32768,), kernel=1), _c(64, 64, (32769,), kernel=1), _c(512, 64, (1024,), kernel=1), _c(544, 64, (1024,), kernel=1), _c(512, 192, (8192,), kernel=1),
+          _c(512, 256, (8192,), kernel=1), _c(64, 192, (1024,), kernel=1, pre="tuple", pre_act="silu"), _c(64, 192, (32, 32), n=2, kernel=1, pre="tuple", res=True, post_act="silu"),
+          _c(64, 192, (1024,), n=2, dtype="fp32", kernel=1, pre="tuple")]
+    for rows, cin in ((128, 64), (129, 64), (16, 384), (16, 416), (16, 512)):
+        S.append(_c(cin, 192, (1024,), kernel=1, packed=True, pre=("recipe", rows)))
+    S += [_c(64, 192, (1024,), kernel=1, pre=("recipe", 16), dtype="fp32"), _c(64, 16, (1024,), kernel=1, pre=("recipe", 16)), _c(64, 192, (1000,), kernel=1, pre=("recipe", 16)),
+          _c(64, 192, (1024,), kernel=1, pre=("recipe", (16, 24))), _c(64, 192, (1024,), kernel=1, pre=("recipe_done", 16)), _c(48, 192, (1024,), kernel=1, pre=("recipe", (16, 8))),
+          _c(64, 192, (1024,), kernel=1, pre=("recipe", 16), transposed=True), _c(64, 192, (1024,), kernel=1, pre=("recipe", 16), res=True),
+          _c(64, 192, (16, 8, 8), n=2, kernel=1, pre=("recipe", 16), pre_act="silu", post_act="silu"), _c(64, 192, (1024,), n=2, kernel=1, pre=("recipe", (16, 32, (32, 32))))]
+    for dt in ("bf16", "fp32"):
+        for tokens in (1024, 1000):
+            S += [_c(64, 192, (tokens,), dtype=dt, kernel=1, packed=True, vt=True), _c(64, 192, (tokens,), dtype=dt, kernel=1, packed=True, vt=True, pre="tuple"),
+                  _c(64, 192, (tokens,), dtype=dt, kernel=1, packed=True, vt=True, pre=("recipe", 16))]
+    S += [_c(64, 192, (1024,), kernel=1, vt=True, res=True), _c(64, 192, (1024,), kernel=1, vt=True, post_act="silu"), _c(64, 192, (1024,), kernel=1, vt=True, pre=("tuple", 67)),
+          _c(64, 192, (1024,), kernel=1, vt=True, pre=("recipe", 16), res=True), _c(64, 192, (1024,), kernel=1, pre=("tuple", "fp64")), _c(64, 192, (1024,), kernel=1, pre="tuple_bad_shape"),
+          _c(64, 192, (1024,), kernel=1, out="bad"), _c(64, 192, (1024,), kernel=1, res="bad"), _c(64, 192, (1024,), kernel=1, out=True, res=True),
+          _c(64, 192, (1024,), kernel=1, rowvec="1"), _c(64, 192, (1024,), kernel=1, want_stats=True), _c(64, 192, (1024,), kernel=1, skip=(64,)), _c(64, 192, (1024,), kernel=1, force_cfg=9),
+          _c(64, 192, (1024,), kernel=1, ksplit=2), _c(36, 192, (1024,), kernel=1), _c(64, 192, (1024,), kernel=1, x_view=(4, 0)), _c(64, 192, (1024,), kernel=1, x_view=(8, 4)),
+          _c(64, 192, (1024,), kernel=1, padding=1), _c(64, 192, (1024,), kernel=1, stride=2), _c(64, 192, (1024,), kernel=1, upsample=True), _c(64, 192, (1024,), kernel=1, transposed=True),
+          _c(64, 192, (1024,), kernel=1, transposed=True, output_padding=1, stride=2), _c((32, 32), 192, (1024,), kernel=1), _c(64, 192, (1024,), kernel=1, pre=("tuple", 67), out=True, res=True),
+          _c(256, 768, 32, kernel=1, packed=True, pre="tuple"), _c(256, 768, 32, kernel=1, packed=True, pre="tuple", attrs=dict(GN_APPLY_POLICY="prologue")),
+          _c(256, 256, 32, kernel=1, res=True)]
+    # -- conv_in of 2-D networks (C_in <= 4 as a depth-1 volume)
+    S += [_c(1, 32, (64, 64), n=16, want_stats=True), _c(5, 32, (64, 64), want_stats=True), _c(3, 64, (64, 64), dtype="fp32", res=True, out=True, rowvec="1", post_act="silu", want_stats=True),
+          _c(1, 32, (64, 64), out=True), _c(4, 32, (8, 8)), _c(1, 36, (64, 64)), _c(1, 32, (64, 64), pre_act="silu"), _c(1, 32, (64, 64), ksplit=2), _c(1, 32, (64, 64), stride=2),
+          _c(1, 32, (64, 64), packed=True), _c(1, 32, (64, 64), padding=0, pad_hi=1), _c(1, 32, (64, 64), attrs=dict(EDGE_2D_AS_3D=False), want_stats=True)]
+    # -- 2-D 3x3 convolutions on cfg 25: stride 1 / 2, the two paddings, up-sampled input, recipes, shortcuts
+    S += [_c(32, 32, (64, 64), stride=2, want_stats=True), _c(32, 32, (64, 64), stride=2, padding=0, pad_hi=1, want_stats=True), _c(32, 32, (64, 64), stride=2, padding=0),
+          _c(32, 32, (64, 64), stride=2, attrs=dict(NARROW_N_2D_STRIDE2=False)), _c(32, 32, (64, 64), attrs=dict(NARROW_N_2D=False), want_stats=True),
+          _c(32, 1, (64, 64)), _c(32, 1, (64, 64), attrs=dict(NARROW_N_2D=False)), _c(32, 1, (64, 64), n=16, pre=("recipe", 16), pre_act="silu"),
+          _c(64, 64, (32, 32), n=16, upsample=True, want_stats=True), _c(32, 64, (64, 64), pre=("recipe", 16), pre_act="silu", rowvec="1", want_stats=True),
+          _c(32, 64, (64, 64), pre=("recipe", 129), pre_act="silu"), _c((64, 32), 32, (64, 64), n=16, pre=("recipe", 64), pre_act="silu", skip=(64, 32), want_stats=True),
+          _c(64, 64, (512, 512), n=16), _c(32, 32, (64, 64), attrs=dict(NARROW_N_2D_MAX_FLOP=1.0)), _c(32, 32, (64, 64), dilation=2), _c(32, 32, (64, 64), kernel=(1, 3), padding=(0, 1)),
+          _c(32, 32, (64, 64), pre="tuple", pre_act="silu", res=True), _c(32, 64, (64, 64), pre="tuple", skip=(32,))]
+    # -- up-sampling: sub-pixel launch or folded into the indexing
+    S += [_c(128, 128, 20, upsample=True, allow_subpixel=False, want_stats=True), _c(128, 128, 20, upsample=True, pre="tuple", pre_act="silu"),
+          _c(128, 128, 20, upsample=True, attrs=dict(SUBPIXEL_UPSAMPLE=False)), _c(128, 128, 20, upsample=True, res=True, out=True, rowvec="n", post_act="silu", n=2, want_stats=True),
+          _c(128, 128, 20, upsample=True, out="bad"), _c(128, 128, 20, upsample=True, res="bad"), _c(128, 128, 20, upsample=True, rowvec="bf16"), _c(128, 128, 20, upsample=True, rowvec="wide"),
+          _c(64, 64, 64, upsample=True, dtype="fp32"), _c(128, 128, (4, 4, 8), upsample=True), _c(128, 128, 20, upsample=True, bias=False), _c(128, 128, 20, upsample=True, ksplit=2),
+          _c(48, 128, 20, upsample=True), _c(128, 12, 20, upsample=True), _c(128, 128, 20, upsample=True, x_view=(4, 0)), _c(128, 128, 20, upsample=True, dilation=2),
+          _c(128, 128, 20, upsample=True, stride=2), _c((64, 64), 128, 20, upsample=True), _c(128, 128, 20, upsample=True, skip=(128,)), _c(128, 128, 20, upsample=True, force_cfg=11),
+          _c(128, 128, 20, upsample=True, packed=True), _c(128, 128, 20, upsample=True, transposed=True), _c(256, 256, 8, upsample=True), _c(64, 64, (1024,), upsample=True),
+          _c(128, 128, 20, upsample=True, out="pad4"), _c(128, 128, 20, upsample=True, res="pad4"), _c(64, 64, 32, upsample=True, transposed=True, dilation=2)]
+    # -- transposed convolutions: stride 2 as a sub-pixel launch (k = 3 with output_padding 1, k = 4), what the rule refuses, stride 1
+    S += [_c(64, 64, 16, transposed=True, stride=2, padding=1, output_padding=1, want_stats=True), _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=1),
+          _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=0), _c(64, 64, 16, transposed=True, stride=2, padding=1), _c(64, 64, 16, transposed=True, stride=2, padding=0, output_padding=1),
+          _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=1, dtype="fp32", res=True), _c(64, 64, 16, transposed=True), _c(64, 64, 32, transposed=True, dtype="fp32"),
+          _c(64, 32, 128, transposed=True), _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=1, attrs=dict(TRANSPOSED_S2_SUBPIXEL=False)),
+          _c(64, 64, (32, 32), transposed=True, stride=2, kernel=4, padding=1), _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=(1, 1, 0)),
+          _c(48, 64, 16, transposed=True, stride=2, kernel=4, padding=1), _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=1, pre="tuple"),
+          _c(64, 64, (4, 4, 8), transposed=True, stride=2, kernel=4, padding=1), _c(4, 64, 32, transposed=True), _c(64, 64, 16, transposed=True, stride=2, kernel=2, padding=0),
+          _c(64, 64, 16, transposed=True, stride=2, kernel=4, padding=1, dilation=2)]
+    # -- dilation, k = 4 stride 2, odd geometries, kernels that do not fit
+    S += [_c(64, 64, 32, dilation=2, pre="tuple", want_stats=True), _c(64, 64, 32, kernel=4, stride=2, padding=1), _c(1, 64, 64, kernel=4, stride=2, padding=1), _c(64, 64, 32, kernel=1),
+          _c(64, 64, 32, kernel=(1, 3, 3)), _c(64, 64, 32, kernel=5), _c(512, 512, 32, dtype="fp32", kernel=7, dilation=4), _c(64, 64, 32, padding=0), _c(64, 64, 2, padding=0),
+          _c(64, 64, 32, stride=(1, 2, 2)), _c(64, 64, 32, padding=(1, 1), kernel=3), _c(64, 32, 32, weight_cin=32), _c(64, 64, ()), _c(64, 64, (4, 4, 4, 4)),
+          _c(64, 64, 64, stride=2, padding=0, pad_hi=1, want_stats=True), _c(64, 64, 64, stride=2, pre="tuple"), _c(128, 128, 32, stride=2, dtype="fp32")]
+    # -- C_out = 1 heads (cfg 20 marching / cfg 13) and C_in <= 4 volumes (cfg 12)
+    S += [_c(32, 1, 128), _c(32, 1, 128, dtype="fp32"), _c(64, 1, 16), _c(64, 1, 64, n=2), _c(64, 1, 256), _c(64, 1, 128, pre="tuple", pre_act="silu"), _c(64, 1, (4, 128, 128)), _c(128, 1, 64),
+          _c(64, 1, 128, attrs=dict(COUT1_MARCH=False)), _c(48, 1, 64), _c(64, 2, 128), _c(64, 16, 128, dtype="fp32"), _c(64, 1, 32, attrs=dict(NARROW_N=False)),
+          _c(1, 64, 128, want_stats=True), _c(1, 64, 128, dtype="fp32", want_stats=True), _c(3, 32, 32), _c(4, 16, 16), _c(1, 32, 4), _c(2, 64, 64, stride=2), _c(4, 64, 32, packed=True),
+          _c(1, 64, 32, force_cfg=12, packed=True), _c(1, 1, 64), _c(1, 64, 64, pre="tuple")]
+    # -- VirtualCat: read in place by the LDS-DMA kernels, else one copied / activated tensor first
+    S += [_c((64, 64), 64, 32), _c((64, 64), 64, 128, want_stats=True), _c((64, 64), 64, 128, pre="tuple", pre_act="silu"), _c((48, 16), 32, (32, 32), kernel=1, pre="tuple", pre_act="silu"),
+          _c((40, 24), 32, (32, 32)), _c((2, 2), 32, (64, 64)), _c((64, 64), 64, 32, cat_mismatch=True), _c((64, 64), 64, 32, pre=("recipe", (16, 32, (96, 32)))), _c((64, 64), 64, 32, dilation=2, skip=(64, 64)),
+          _c((64, 64), 64, 32, force_cfg=11), _c((64, 64), 64, 32, force_cfg=9), _c((128, 128), 128, 64, dtype="fp32", pre="tuple", skip=(128, 128), rowvec="1", want_stats=True),
+          _c((32, 32), 32, (64, 64), n=16, pre=("recipe", 16), pre_act="silu", rowvec="n", want_stats=True), _c((64, 64), 64, (1024,))]
+    # -- the 1x1 shortcut: fused as extra K chunks, or as 1x1 launches first
+    S += [_c(128, 64, 32, skip=(64,), pre="tuple", pre_act="silu", want_stats=True), _c(128, 64, 32, skip=(64, 64), want_stats=True), _c(64, 128, 128, skip=(64,), want_stats=True),
+          _c(64, 128, 32, dilation=2, skip=(64,)), _c(64, 128, 32, dilation=2, skip=(64, 64), pre="tuple", want_stats=True, rowvec="1"), _c(64, 128, (1024,), skip=(32, 32)),
+          _c(64, 64, 32, skip=(64,), res=True), _c(64, 64, 32, skip=(32, 16, 16)), _c(64, 64, 32, skip=(64, dict(cout_off=1))), _c(64, 64, 32, skip=(64, dict(bad_geometry=True))),
+          _c(64, 64, 32, skip=(64, dict(bias=False))), _c(48, 64, 32, skip=(48,)), _c(64, 64, 128, pre="tuple", skip=(32,), want_stats=True), _c(64, 8, 32, skip=(64,)),
+          _c(256, 256, 16, skip=(128, 128), pre=("recipe", 16)), _c(128, 128, 16, skip=(64,)), _c(64, 64, 16, skip=(128,))]
+    # -- split-K: the policy, forced slice counts, what must raise
+    S += [_c(256, 256, 16, ksplit=2), _c(384, 128, 16, ksplit=8), _c(384, 128, 16), _c(256, 256, 16, ksplit=1), _c(256, 256, 16, ksplit=64), _c(256, 256, 16, ksplit=4, out="pad4"),
+          _c(256, 256, 16, out="pad4"), _c(64, 64, 128, ksplit=4), _c(256, 256, 16, want_stats=True, res=True), _c(256, 256, 16, dtype="fp32", pre="tuple", want_stats=True),
+          _c(256, 256, 32), _c(256, 128, (16, 16, 32)), _c(64, 64, 32, ksplit=2, want_stats=True), _c(256, 256, 16, stride=2, ksplit=2), _c(512, 512, 8, n=2), _c(512, 512, 4),
+          _c(128, 128, 16), _c(192, 192, 16), _c(224, 64, 16), _c(256, 2048, 8), _c(256, 4096, 4, dtype="fp32"),
+          _c(256, 4096, (4, 8, 8), dtype="fp32"), _c(256, 4096, (4, 8, 8), dtype="fp32", ksplit=2), _c(64, 64, 32, attrs=dict(LDS_HARD_LIMIT=80500))]
+    # -- force_cfg inside and outside DMA_CFGS
+    for cfg in (11, 14, 16, 18, 19, 24, 25, 17, 4, 0, 9, 10, 21, 12, 13, 20):
+        S.append(_c(64, 64, 64, force_cfg=cfg, want_stats=True))
+    S += [_c(64, 64, 64, force_cfg=11, pre="tuple"), _c(64, 64, 64, force_cfg=14, pre="tuple"), _c(64, 64, 64, force_cfg=4, pre="tuple", skip=(64,)), _c(64, 64, 64, force_cfg=24, pre=("recipe", 16)),
+          _c(64, 64, 16, force_cfg=11, pre=("recipe", 16)), _c(32, 32, (64, 64), force_cfg=25), _c(32, 32, (64, 64), force_cfg=8), _c(32, 32, (64, 64), force_cfg=11), _c(64, 64, 64, stride=2, force_cfg=15),
+          _c(64, 1, 64, force_cfg=20), _c(64, 1, 64, force_cfg=13), _c(64, 64, 16, force_cfg=11, ksplit=2)]
+    # -- where a pending GroupNorm is finalised: descriptor (cfg 24 / 25), K slices, or the finalisation launch
+    S += [_c(64, 64, 32, pre=("recipe", 16), pre_act="silu", want_stats=True), _c(64, 64, 32, pre=("recipe", 128)), _c(64, 64, 32, pre=("recipe", 129)), _c(64, 64, 32, pre=("recipe_done", 16)),
+          _c(256, 256, 16, pre=("recipe", 16), pre_act="silu", want_stats=True), _c(256, 256, 16, pre=("recipe", 129)), _c(256, 256, 16, pre=("recipe", 16), ksplit=1),
+          _c(256, 256, 16, pre=("recipe", 16), ksplit=4), _c(256, 256, 16, pre=("recipe", 16), out="pad4"), _c(64, 64, 128, pre=("recipe", 16), want_stats=True), _c(64, 64, 64, pre=("recipe", 16)),
+          _c(64, 64, 32, pre=("recipe", 16), stride=2), _c(64, 64, 32, pre=("recipe", 16), dilation=2), _c(64, 64, 32, pre=("recipe", 16), upsample=True), _c(64, 64, 32, pre=("recipe", 16), transposed=True),
+          _c(64, 4, 32, pre=("recipe", 16), pre_act="silu"), _c(384, 128, 16, pre=("recipe", 16)), _c(448, 128, 16, pre=("recipe", 16)), _c(64, 64, 32, n=2, pre=("recipe", 16)),
+          _c(64, 64, 32, pre=("recipe", (16, 8))), _c(48, 48, 32, pre=("recipe", (16, 8))), _c(64, 64, 32, pre=("recipe", 16), kernel=1), _c(64, 64, 32, pre="tuple_bad_shape"),
+          _c(64, 64, 32, pre=("tuple", "fp64")), _c(64, 64, (1024,), pre=("recipe", 16)), _c(64, 64, 32, pre=("recipe", 16), kernel=(1, 3, 3))]
+    # -- operand checks of the tile-kernel path
+    S += [_c(64, 64, 32, out="bad"), _c(64, 64, 32, out="f32"), _c(64, 64, 32, res="bad"), _c(64, 64, 32, res="f32"), _c(64, 64, 32, rowvec="bf16"), _c(64, 64, 32, rowvec="strided"),
+          _c(64, 64, 32, rowvec="wide"), _c(64, 64, 32, n=2, rowvec="n", res=True, out=True, post_act="silu", want_stats=True), _c(64, 64, 32, bias=False, out="pad4", res="pad4", want_stats=True),
+          _c(64, 64, 32, x_view=(4, 0)), _c(64, 64, 32, x_view=(8, 4)), _c(64, 64, 32, weight_dtype=torch.float32), _c(64, 64, 32, dtype="fp32", weight_dtype=torch.bfloat16)]
+    # -- every policy attribute a test, a tool or an A/B script assigns, on the cases it governs
+    for attrs in (dict(DMA_FUSED_PROLOGUE="always"), dict(DMA_FUSED_PROLOGUE="never"), dict(DMA_FUSED_PROLOGUE=True), dict(DMA_FUSED_PROLOGUE="1"), dict(GN_APPLY_POLICY="prologue"),
+                  dict(GN_APPLY_POLICY="pass")):
+        S += [_c(64, 64, 128, pre="tuple", pre_act="silu", want_stats=True, attrs=attrs), _c(64, 64, 32, pre="tuple", pre_act="silu", want_stats=True, attrs=attrs),
+              _c((64, 64), 64, 32, pre="tuple", attrs=attrs), _c(64, 64, 32, pre=("recipe", 16), attrs=attrs), _c(64, 64, 8, pre="tuple", attrs=attrs),
+              _c(48, 48, 32, pre="tuple", attrs=attrs), _c(64, 64, 128, dtype="fp32", pre="tuple", attrs=attrs)]
+    S += [_c(64, 64, 128, attrs=dict(DMA_WIDE_WAVES=False)), _c(256, 256, 32, attrs=dict(DMA_WIDE_WAVE_MIN_TILES=4096)), _c(64, 64, 128, attrs=dict(DMA_CONV=False), want_stats=True),
+          _c(64, 64, 32, attrs=dict(DMA_CONV=False)), _c(64, 64, 16, attrs=dict(DMA_CONV_MIN_VOXELS=1 << 16)),
+          _c(256, 256, 16, attrs=dict(SPLITK=False)), _c(256, 256, 16, attrs=dict(SPLITK=False), pre=("recipe", 16)), _c(64, 64, 32, attrs=dict(SPLITK=False)), _c(256, 256, 16, attrs=dict(SPLITK=False), ksplit=4),
+          _c(64, 64, 32, attrs=dict(NARROW_N=False)), _c(64, 4, 32, attrs=dict(NARROW_N=False)), _c(64, 64, 32, attrs=dict(NARROW_N=False), pre=("recipe", 16)),
+          _c(256, 256, 16, attrs=dict(NARROW_N_MAX_CHUNKS=8)), _c(256, 256, 16, attrs=dict(NARROW_N_MAX_CHUNKS=7)), _c(192, 64, 16, attrs=dict(NARROW_N_MAX_CHUNKS=5)), _c(64, 64, 32, attrs=dict(NARROW_N_MAX_CHUNKS=1)),
+          _c(128, 64, 32, skip=(64, 64), attrs=dict(NARROW_N_MAX_CHUNKS=7)), _c(128, 64, 32, skip=(64, 64), attrs=dict(NARROW_N_MAX_CHUNKS=8)),
+          _c(64, 192, (1024,), kernel=1, attrs=dict(TOKEN_GEMM=False)), _c(64, 192, (1024,), kernel=1, attrs=dict(TOKEN_GEMM_MAX_ROWS=512)), _c(64, 192, (1024,), kernel=1, attrs=dict(TOKEN_GEMM_MAX_ROWS=1024)),
+          _c(64, 192, (1024,), kernel=1, attrs=dict(TOKEN_GEMM_MAX_FLOP=1.0e7)), _c(256, 768, (32768,), kernel=1, packed=True, pre="tuple", vt=True, attrs=dict(TOKEN_GEMM_MAX_FLOP=1.0e11)),
+          _c(256, 768, (32768,), kernel=1, packed=True, pre="tuple", vt=True), _c(64, 192, (1024,), kernel=1, attrs=dict(TOKEN_GEMM_MAX_CIN=32)),
+          _c(64, 192, (1024,), kernel=1, pre=("recipe", 16), attrs=dict(GN_IN_TOKEN_GEMM=False)), _c(64, 192, (1024,), kernel=1, pre=("recipe", 16), attrs=dict(GN_IN_CONSUMER_MAX_ROWS=8)),
+          _c(256, 256, 16, pre=("recipe", 16), attrs=dict(GN_IN_SPLIT_SLICES=False)), _c(64, 256, (8,), kernel=1, attrs=dict(SMALL_LINEAR_ROWS=4)),
+          _c(256, 256, 16, attrs=dict(SPLITK_TARGET_WGS=512)), _c(512, 512, 8, attrs=dict(SPLITK_TARGET_WGS=64)), _c(256, 256, 16, attrs=dict(SPLITK_MAX=2)), _c(256, 256, 16, attrs=dict(SPLITK_MAX_TILES=16)),
+          _c(64, 4, 32, attrs=dict(NARROW_HEAD_MAX_FLOP=1.0)), _c(64, 64, 32, pre="tuple", attrs=dict(DMA_FUSED_PROLOGUE_MAX_FLOP=1.0)), _c(64, 1, 128, attrs=dict(COUT1_MARCH_LTW_128B=5)),
+          _c(128, 128, 20, upsample=True, attrs=dict(STRIDE2_DGRAD_SUBPIXEL=False)), _c(64, 64, 128, attrs=dict(LDS_SOFT_LIMIT=1024)), _c(64, 16, 128, dtype="fp32", attrs=dict(LDS_SOFT_LIMIT=1024)),
+          _c(64, 64, 128, want_stats=True, attrs=dict(STATS_COMPACT_ABOVE=1 << 30))]
+    # -- the layers of the five benchmark configurations
+    for dt in ("bf16", "fp32"):
+        S += _unet_layer_cases(3, 128, (64, 128, 256), 1, 1, dtype=dt) + _attention_cases(256, 32 ** 3, dtype=dt)                       # C2: 1 x 1 x 128^3
+    S += _unet_layer_cases(3, 32, (64, 128, 256), 4, 4, recipe_rows=16) + _attention_cases(128, 16 ** 3) + _attention_cases(256, 8 ** 3)    # C3: the latent UNet, 32^3 / 16^3 / 8^3
+    S += _unet_layer_cases(3, 32, (64, 128, 256), 4, 4, dtype="fp32")
+    for dt in ("bf16", "fp32"):
+        S += _unet_layer_cases(2, 64, (32, 64), 1, 1, n=16, dtype=dt, recipe_rows=16) + _attention_cases(64, 32 * 32, n=16, dtype=dt)   # configs[0]: 16 x 1 x 64 x 64
+    S += _unet_layer_cases(3, 32, (128, 256, 512), 4, 4, n=2, recipe_rows=16) + _attention_cases(512, 8 ** 3, n=2)                       # C4: the 41.7 M-parameter UNet's levels
+    for size in (64, 128, 256):  # the autoencoders: 64 -> 64 at full resolution, the Downsample (pad high only), encoder / decoder ends
+        S += [_c(64, 64, size, pre="tuple", pre_act="silu", want_stats=True), _c(64, 64, size, pre="tuple", pre_act="silu", res=True, want_stats=True), _c(1, 64, size, want_stats=True),
+              _c(64, 64, size, stride=2, padding=0, pad_hi=1, want_stats=True), _c(64, 1, size, pre="tuple", pre_act="silu"), _c(64, 128, size // 2, pre="tuple", pre_act="silu", skip=(64,), want_stats=True),
+              _c(128, 64, size // 2, upsample=True, want_stats=True)]
+    S += [_c(128, 8, 16, pre="tuple", pre_act="silu"), _c(4, 4, 16, kernel=1), _c(4, 128, 16, want_stats=True), _c(128, 128, 16, upsample=True, allow_subpixel=False, want_stats=True),
+          _c(1, 256, 64, kernel=4, stride=2, padding=1), _c(256, 256, 32, kernel=4, stride=2, padding=1), _c(256, 256, 16, res=True), _c(256, 32, 16, kernel=1), _c(32, 256, 16),
+          _c(256, 256, 16, transposed=True, stride=2, kernel=4, padding=1), _c(256, 1, 32, transposed=True, stride=2, kernel=4, padding=1)]
+    return S
+
+
+def _conv_route_census(write=None, parent=None):
+    """{case id: records}; write=path stores it as the golden table (to be run at the commit the table is meant to describe)."""
+    import io
+    import json
+    table = {}
+    for case in _conv_route_cases():
+        cid = json.dumps(case, sort_keys=True, default=str)
+        if cid not in table:  # (the networks share layers: the same case from two of them is run once)
+            table[cid] = _run_conv_route_case(case)
+    if write is not None:
+        import gzip
+        with gzip.GzipFile(write, "wb", compresslevel=9, mtime=0) as raw, io.TextIOWrapper(raw) as fh:
+            fh.write('{"recorded_at_commit": %s,\n "cases": {\n' % json.dumps(parent))
+            fh.write(",\n".join(f"  {json.dumps(k)}: {json.dumps(v, separators=(',', ':'))}" for k, v in table.items()))
+            fh.write("\n }}\n")
+    return table
+
+
+def test_conv_routes_match_the_table_recorded_before_the_split_into_planner_and_launchers():
+    """ops.conv / ops.linear driven on CPU tensors over the case matrix above, every launching entry point of the library replaced by a recorder
+    (_util.conv_on_cpu): for every case the same entry points in the same order with the same arguments and descriptors as
+    tests/golden/conv_routes.json.gz, which was recorded with this harness at the parent commit of the refactor (named in the file)."""
+    import gzip
+    import json
+    import os
+
+    from _util import GOLDEN
+    from generativemodels_amd import _native as nat
+    with gzip.open(os.path.join(GOLDEN, "conv_routes.json.gz"), "rt") as fh:
+        want = json.load(fh)["cases"]
+    got = json.loads(json.dumps(_conv_route_census()))
+    assert list(got) == list(want), "the case matrix and the recorded table list different cases"
+    fields = [f for f, _ in nat.GmConvDesc._fields_]
+    bad = []
+    for cid in want:
+        if got[cid] != want[cid]:
+            detail = ""
+            for a, b in zip(got[cid], want[cid]):
+                if a != b and a[0] == b[0] and len(a) > 1 and isinstance(a[1], list) and len(a[1]) == len(fields) == len(b[1]):
+                    detail = f" {a[0]}: " + ", ".join(f"{f} {y} -> {x}" for f, x, y in zip(fields, a[1], b[1]) if x != y)
+                    break
+            bad.append(f"{cid}: {[r[0] for r in want[cid]]} -> {[r[0] for r in got[cid]]}{detail}")
+    assert not bad, f"{len(bad)} of {len(want)} cases changed their launches:\n" + "\n".join(bad[:40])
