@@ -27,7 +27,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 _MIRRORED = ["", ".networks", ".networks.nets", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.schedulers", ".networks.layers",
-             ".inferers", ".utils"]
+             ".inferers", ".utils", ".metrics"]
 
 
 def install_as_generative(force: bool = False) -> None:

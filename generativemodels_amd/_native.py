@@ -178,6 +178,13 @@ PROTOTYPES = {
     "gm_vq_ema_stats": (C.c_int, [c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_int, c_vp, c_vp, C.c_int, c_vp]),
     "gm_vq_ema_update": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_float, C.c_float, c_vp]),
     "gm_vq_gather": (C.c_int, [c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, c_vp]),
+    "gm_ssim_max_window": (C.c_int, []),
+    "gm_ssim_workspace_bytes": (c_ll, [c_ll, c_ll] + [C.c_int] * 6),
+    "gm_ssim_cs": (C.c_int, [c_vp, c_vp, C.c_int, c_ll, c_ll, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int,
+                             C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]),
+    "gm_avgpool2_pair": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
+    "gm_mmd_workspace_bytes": (c_ll, [c_ll, c_ll]),
+    "gm_mmd": (C.c_int, [c_vp, c_vp, C.c_int, c_ll, c_ll, c_vp, c_vp, c_ll, c_vp]),
 }
 
 _lib = None

@@ -2367,3 +2367,103 @@ def vq_gather(indices: torch.Tensor, embedding: torch.Tensor, dtype: torch.dtype
                              _ptr(err), _ptr(ws), indices.numel(), emb.shape[0], emb.shape[1], dt_code(dtype), _stream()),
           "gm_vq_gather")
     return (out, err) if x is not None else out
+
+
+# ---- generative.metrics (csrc/metrics.hip) ---------------------------------------------------------------------------------------------
+_METRIC_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # the metric kernels upcast in registers and also read fp16
+
+
+def metric_dt_code(dtype: torch.dtype) -> int:
+    try:
+        return _METRIC_DT[dtype]
+    except KeyError:
+        raise TypeError(f"the metric kernels read float32, bfloat16 and float16, got {dtype}") from None
+
+
+def ssim_max_window() -> int:
+    """Taps per axis the SSIM kernel is built for."""
+    return int(lib().gm_ssim_max_window())
+
+
+def _volumes(t: torch.Tensor):
+    """(B, C, D, H, W) of an NCHW / NCDHW tensor (2-D: D = 1)."""
+    if t.dim() == 4:
+        return t.shape[0], t.shape[1], 1, t.shape[2], t.shape[3]
+    if t.dim() == 5:
+        return tuple(t.shape)
+    raise ValueError(f"expected a (B, C, H, W) or (B, C, D, H, W) tensor, got {t.dim()} dimensions")
+
+
+def ssim_cs(x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]], c1: float, c2: float, want_maps: bool = False):
+    """SSIM and contrast sensitivity of two NC[D]HW images under a separable window: `taps` holds one normalised 1-D table per spatial axis.
+    -> (ssim_mean (B,), cs_mean (B,), ssim_map, cs_map): fp32 means over channels and "valid" positions, and the fp32 maps
+    (B, C, *valid extents) or None."""
+    require_device(x, y)
+    if x.shape != y.shape or x.dtype != y.dtype:
+        raise ValueError(f"ssim_cs operands must share shape and dtype, got {tuple(x.shape)} {x.dtype} and {tuple(y.shape)} {y.dtype}")
+    B, Cn, D, H, W = _volumes(x)
+    nsp = x.dim() - 2
+    if len(taps) != nsp:
+        raise ValueError(f"ssim_cs needs one tap table per spatial axis ({nsp}), got {len(taps)}")
+    tabs = ([[1.0]] if nsp == 2 else []) + [[float(v) for v in t] for t in taps]
+    kd, kh, kw = (len(t) for t in tabs)
+    limit = ssim_max_window()
+    if min(kd, kh, kw) < 1 or max(kd, kh, kw) > limit:
+        raise ValueError(f"SSIM window sizes must be 1..{limit} per axis (the built limit), got {tuple(len(t) for t in taps)}")
+    if kd > D or kh > H or kw > W:
+        raise ValueError(f"SSIM window {tuple(len(t) for t in taps)} is larger than the image {tuple(x.shape[2:])}")
+    if B * Cn == 0 or B * Cn > 65535:
+        raise ValueError(f"ssim_cs takes 1..65535 (batch x channel) volumes, got {B * Cn}")
+    x, y = x.contiguous(), y.contiguous()
+    ws_bytes = int(lib().gm_ssim_workspace_bytes(B, Cn, D, H, W, kd, kh, kw))
+    if ws_bytes < 0:
+        raise ValueError("ssim_cs: geometry refused by the planner")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    means = torch.empty((2, B), dtype=torch.float32, device=x.device)
+    out_sp = (D - kd + 1, H - kh + 1, W - kw + 1)[3 - nsp:]
+    maps = torch.empty((2, B, Cn, *out_sp), dtype=torch.float32, device=x.device) if want_maps else None
+    ctabs = [(C.c_float * len(t))(*t) for t in tabs]
+    nout = float(B * Cn * math.prod(out_sp))
+    _timed("ssim_cs", dict(flops=nout * (10.0 * (kd + kh + kw) + 20.0), bytes=float(2 * x.element_size() * x.numel() + (8.0 * nout if want_maps else 0.0)),
+                           shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_ssim_cs(x.data_ptr(), y.data_ptr(), metric_dt_code(x.dtype), B, Cn, D, H, W, ctabs[0], kd, ctabs[1], kh, ctabs[2], kw,
+                                          float(c1), float(c2), means[0].data_ptr(), means[1].data_ptr(), _ptr(None if maps is None else maps[0]),
+                                          _ptr(None if maps is None else maps[1]), ws.data_ptr(), ws_bytes, _stream()), "gm_ssim_cs"))
+    return means[0], means[1], (None if maps is None else maps[0]), (None if maps is None else maps[1])
+
+
+def avgpool2_pair(a: torch.Tensor, b: torch.Tensor):
+    """avg_pool{2,3}d(kernel_size=2) of two NC[D]HW images in one launch (floor on odd extents) -> two fp32 tensors."""
+    require_device(a, b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        raise ValueError("avgpool2_pair operands must share shape and dtype")
+    B, Cn, D, H, W = _volumes(a)
+    three_d = a.dim() == 5
+    if B * Cn == 0 or min(H, W) < 2 or (three_d and D < 2):
+        raise ValueError(f"avgpool2_pair: every spatial extent must be at least 2, got {tuple(a.shape[2:])}")
+    a, b = a.contiguous(), b.contiguous()
+    out_sp = ((D // 2,) if three_d else ()) + (H // 2, W // 2)
+    out = torch.empty((2, B, Cn, *out_sp), dtype=torch.float32, device=a.device)
+    _timed("avgpool2_pair", dict(flops=float(2 * a.numel()), bytes=float(2 * a.element_size() * a.numel() + 4 * out.numel()), shape=str(tuple(a.shape))),
+           lambda: check(lib().gm_avgpool2_pair(a.data_ptr(), b.data_ptr(), metric_dt_code(a.dtype), out[0].data_ptr(), out[1].data_ptr(), B * Cn, D, H, W,
+                                                int(three_d), _stream()), "gm_avgpool2_pair"))
+    return out[0], out[1]
+
+
+def mmd_terms(y: torch.Tensor, y_pred: torch.Tensor) -> torch.Tensor:
+    """MMDMetric's value for (B, F) views of two samples: 1.0 * (mean(y y^T / F) + mean(p p^T / F)) - 2.0 * mean(p y^T / F) as a 0-dim fp32 tensor,
+    from the column sums of y and p (no Gram matrix)."""
+    require_device(y, y_pred)
+    if y.dim() != 2 or y.shape != y_pred.shape or y.dtype != y_pred.dtype:
+        raise ValueError(f"mmd_terms takes two (B, F) tensors of one shape and dtype, got {tuple(y.shape)} {y.dtype} and {tuple(y_pred.shape)} {y_pred.dtype}")
+    B, F = y.shape
+    if B == 0 or F == 0:
+        raise ValueError("mmd_terms: empty input")
+    y, y_pred = y.contiguous(), y_pred.contiguous()
+    ws_bytes = int(lib().gm_mmd_workspace_bytes(B, F))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+    out = torch.empty((1,), dtype=torch.float32, device=y.device)
+    _timed("mmd", dict(flops=float(2 * y.numel() + 6 * F), bytes=float(2 * y.element_size() * y.numel()), shape=str(tuple(y.shape))),
+           lambda: check(lib().gm_mmd(y.data_ptr(), y_pred.data_ptr(), metric_dt_code(y.dtype), B, F, out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+                         "gm_mmd"))
+    return out[0]

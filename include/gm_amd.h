@@ -480,6 +480,28 @@ int gm_vq_gather(const long long* indices, const float* embedding, void* out, lo
                  long long x_ld, float* sq_err_mean, void* workspace, long long tokens, int num_embeddings, int dim,
                  int dtype, void* stream);
 
+/* ---- metrics (metrics/ssim.py, ms_ssim.py, mmd.py) --------------------------------------------------------------------
+ * Inputs here are contiguous NC[D]HW tensors (not arena tensors) of dtype GM_F32, GM_BF16 or GM_F16, upcast in registers; every result is fp32.
+ * Reductions are per-work-group fp64 partials folded in a fixed order: no atomics, bit-reproducible. */
+#define GM_F16 2
+/* SSIM and contrast sensitivity of compute_ssim_and_cs (metrics/ssim.py:169-231) as ONE separable pass: x, y = (B, C, D, H, W) (2-D: D = 1, kd = 1, taps_d = {1}),
+ * one normalised tap table per axis (HOST pointers, 1 .. gm_ssim_max_window() taps, even sizes included), "valid" extents n - k + 1.  ssim_mean / cs_mean [B]:
+ * mean over channels and space.  ssim_map / cs_map: (B, C, Do, Ho, Wo) fp32 or both NULL.  workspace: gm_ssim_workspace_bytes(...) bytes, no initialisation. */
+int gm_ssim_max_window(void);
+long long gm_ssim_workspace_bytes(long long B, long long C, int D, int H, int W, int kd, int kh, int kw);
+int gm_ssim_cs(const void* x, const void* y, int dtype, long long B, long long C, int D, int H, int W, const float* taps_d, int kd,
+               const float* taps_h, int kh, const float* taps_w, int kw, float c1, float c2, float* ssim_mean, float* cs_mean,
+               float* ssim_map, float* cs_map, void* workspace, long long workspace_bytes, void* stream);
+/* avg_pool{2,3}d(kernel_size=2) of both images between two MS-SSIM scales (metrics/ms_ssim.py:140-141): (nvol, D, H, W) -> fp32 (nvol, D / 2, H / 2, W / 2),
+ * floor on odd extents; pool_depth = 0 leaves D as it is (2-D). */
+int gm_avgpool2_pair(const void* a, const void* b, int dtype, float* out_a, float* out_b, long long nvol, int D, int H, int W, int pool_depth,
+                     void* stream);
+/* MMDMetric (metrics/mmd.py:68-80) on (B, F) views: out[0] = 1.0 * (mean(y y^T / F) + mean(p p^T / F)) - 2.0 * mean(p y^T / F), from the column sums of
+ * y and p (mean(Y Y^T) = |sum_i y_i|^2 / B^2): one read of each tensor, no Gram matrix.  workspace: gm_mmd_workspace_bytes(B, F) bytes. */
+long long gm_mmd_workspace_bytes(long long B, long long F);
+int gm_mmd(const void* y, const void* y_pred, int dtype, long long B, long long F, float* out, void* workspace, long long workspace_bytes,
+           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
