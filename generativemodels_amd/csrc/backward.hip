@@ -912,7 +912,17 @@ extern "C" int gm_layernorm_bwd(const void* x, long long x_ld, const void* gy, l
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)gm_layernorm_bwd_slots(rows);
-  const size_t smem = (size_t)4 * C * 2 * sizeof(float);
+  const size_t smem = (size_t)4 * C * 2 * sizeof(float);  // 128 KiB at C = 4096: above the 64 KiB a launch gets unasked from C = 2049 on
+  if (smem > 64 * 1024) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(layernorm_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(layernorm_bwd_kernel<bf16_raw>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      if (e != hipSuccess) { (void)hipGetLastError(); GM_FAIL((int)e, hipGetErrorString(e)); }
+      attr_set = true;
+    }
+  }
   if (dtype == GM_F32)
     layernorm_bwd_kernel<float><<<grid, 256, smem, st>>>((const float*)x, x_ld, (const float*)gy, gy_ld, (float*)dx, dx_ld, gamma, rows, C, eps, param_stats);
   else if (dtype == GM_BF16)

@@ -396,11 +396,14 @@ extern "C" int gm_gn_finalize_channels(const double* stats0, int S0, int C0, con
   GM_REQUIRE(G > 0 && (C0 + C1) % G == 0, "channels must be divisible by groups");
   if (N == 0) return 0;
   const int cpg = (C0 + C1) / G;
-  if (S0 <= GN_SHORT_MAX_ROWS && (C1 == 0 || S1 <= GN_SHORT_MAX_ROWS) && cpg <= 4096) {  // short tables: the order the consumer-side finalisation shares (ops.GnRecipe)
+  // the short kernel's LDS: the group's [cpg + 1] pairs and, staged, its rows -- both within the 64 KiB a launch gets unasked (cpg = 4096 asked for 65 552
+  // bytes, cpg = 2048 with one staged row likewise: wider groups go to the long-table kernel, rows that do not fit are walked unstaged)
+  const size_t sums = (size_t)(2 * cpg + 2) * sizeof(double), lds_max = 64 * 1024;
+  if (S0 <= GN_SHORT_MAX_ROWS && (C1 == 0 || S1 <= GN_SHORT_MAX_ROWS) && sums <= lds_max) {  // short tables: the order the consumer-side finalisation shares (ops.GnRecipe)
     const int smax = C1 && S1 > S0 ? S1 : S0;
     const size_t staged = (size_t)smax * cpg * 2 * sizeof(double);
-    const int staged_rows = staged <= 48 * 1024 ? smax : 0;  // (else: a thread walks its channel's rows itself -- the same sums)
-    gn_finalize_channels_short_kernel<<<N * G, 256, (size_t)(2 * cpg + 2) * sizeof(double) + (staged_rows ? staged : 0), (hipStream_t)stream>>>(
+    const int staged_rows = staged <= 48 * 1024 && sums + staged <= lds_max ? smax : 0;  // (else: a thread walks its channel's rows itself -- the same sums)
+    gn_finalize_channels_short_kernel<<<N * G, 256, sums + (staged_rows ? staged : 0), (hipStream_t)stream>>>(
         stats0, S0, C0, stats1, S1, C1, N, G, V, eps, gamma, beta, scale, shift, staged_rows);
   }
   else
