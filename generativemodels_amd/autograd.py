@@ -9,10 +9,11 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
   group_norm_act  forward: per-channel statistics -> (scale, shift) -> one apply pass (+ SiLU)
                   backward: gm_gn_bwd_stats / _finalize / _apply (dx, dgamma, dbeta)
   upsample_conv   nearest 2x folded into the convolution; backward: dgrad on the fine grid, 2x sum-pool; dW against the upsampled input
-  attention       forward: the flash-attention kernel (head dims up to 256; 257 .. 1024 on the sliced wide-head kernel); backward: the fused
-                  flash backward gm_attention_backward (head dims 16 .. 256: scores recomputed per tile, nothing L x L stored); other head dims
-                  (and every head dim above 256, unpadded) per (sample, head) in fp32 -- scores, softmax, dV = P^T dO, dP = dO V^T,
-                  dS (gm_softmax_bwd), dQ = dS K, dK = dS^T Q -- on the GEMM / weight-gradient kernels (up to 8192 tokens)
+  attention       forward: the flash-attention kernel (head dims up to 256; 257 .. 1024 on the sliced wide-head kernel); backward: one of four
+                  routes, chosen from dtype, (sample, head) pairs, tokens and head dim by the table of attention_backward_route -- the fused
+                  bf16 LDS-DMA flash backward, the bf16-MFMA score pass + weight-gradient kernels, the fused fp32 flash backward (head dims
+                  zero-padded to 16 .. 256 for these two), or per (sample, head) in fp32 on the GEMM / weight-gradient kernels (the only one
+                  for head dims above 256, unpadded, up to 8192 tokens)
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -405,18 +406,69 @@ def activation(x: torch.Tensor, act: str) -> torch.Tensor:
 
 ATTENTION_BWD_MAX_TOKENS = 8192
 ATTENTION_BWD_BF16_MIN_TOKENS = int(__import__("os").environ.get("GM_ATTN_BWD_BF16_MIN_TOKENS", "512"))  # (bench switch: a huge value disables the path)
+ATTENTION_BWD_FUSED_MIN_TOKENS = int(__import__("os").environ.get("GM_ATTN_BWD_FUSED_MIN_TOKENS", "256"))  # (bench switch: a huge value restores the round-4 policy)
 
 
-# (round 5) bf16 operands, head dim 64 / 128 / 256: the fused LDS-DMA flash backward (ops.attention_backward_fused) from this many tokens on.
-# Measured on MI355X (tools/attn_bwd_fused_ab.py, profiles/r05_attn_bwd_fused_ab.txt): 32 768 x 256 3.97 ms against 17-20 composed, 4 096 x 256 0.14
-# against 0.33, 2 x 8 heads x 256 x 64 0.048 against 0.092 (profiles/r05_attn_bwd_fused_policy.txt: every measured shape from 256 tokens on).  (bench switch: a huge value restores the round-4 policy)
-ATTENTION_BWD_FUSED_MIN_TOKENS = int(__import__("os").environ.get("GM_ATTN_BWD_FUSED_MIN_TOKENS", "256"))
+# The routes of the attention backward, consulted in this order; the first predicate that holds names the route.  Each sees (bf16 operands?,
+# (sample, head) pairs, tokens of the longer side, head dim, head dim after zero-padding to a built width) and reads the thresholds when called.
+def _route_fused(bf16, pairs, tokens, dh, dhp):
+    # (round 5) bf16 operands, head dim 64 / 128 / 256: the fused LDS-DMA flash backward (ops.attention_backward_fused) from this many tokens on.
+    # Measured on MI355X (tools/attn_bwd_fused_ab.py, profiles/r05_attn_bwd_fused_ab.txt): 32 768 x 256 3.97 ms against 17-20 composed, 4 096 x 256 0.14
+    # against 0.33, 2 x 8 heads x 256 x 64 0.048 against 0.092 (profiles/r05_attn_bwd_fused_policy.txt: every measured shape from 256 tokens on).
+    return bf16 and dh in ops.ATTENTION_BWD_FUSED_HEAD_DIMS and tokens >= ATTENTION_BWD_FUSED_MIN_TOKENS
+
+
+def _route_wide(bf16, pairs, tokens, dh, dhp):
+    # head dims above the fused backward kernels' 256 (the forward's sliced wide-head kernel): the composed per-(sample, head) fp32 path, unpadded --
+    # its GEMM / weight-gradient / softmax kernels take any head dim -- up to ATTENTION_BWD_MAX_TOKENS per side (it materialises the fp32 Lq x Lk
+    # score matrices; attention_backward_route refuses more)
+    return dh > max(ops.ATTENTION_BWD_HEAD_DIMS)
+
+
+def _route_bf16(bf16, pairs, tokens, dh, dhp):
+    # bf16 operands on the bf16-MFMA score pass + the weight-gradient kernel (ops.attention_backward_bf16: every product at the bf16 MFMA rate;
+    # P, dS, dS^T of the (sample, head) pairs in flight live in HBM, one pair at a time when all of them would not fit): one or two pairs of
+    # >= 512 tokens (C4: one head x 4096 tokens at 16^3, one x 512 at 8^3) -- and ANY number of pairs above 8 192 tokens, where the fused fp32
+    # kernels below run at 45 TFLOP/s (84.6 ms per head at 32 768 x 256 against 16-17 ms here).  Any size: pairs beyond
+    # ops.ATTENTION_BWD_BF16_SLAB_BYTES of score matrices go through in query slabs.
+    return (bf16 and dhp in ops.ATTENTION_BWD_BF16_HEAD_DIMS and tokens >= ATTENTION_BWD_BF16_MIN_TOKENS
+            and (pairs <= 2 or tokens > ATTENTION_BWD_MAX_TOKENS))
+
+
+def _route_flash(bf16, pairs, tokens, dh, dhp):
+    # fp32 (or bf16 below the bounds above): the fused kernels own 64 rows per work-group, so ONE head of a few thousand tokens leaves most CUs
+    # idle (L = 4096, d = 128: 1.9 ms fused vs 0.86 ms composed) while many (sample, head) pairs favour them (2 x 4 heads of 1024 tokens: 0.21 vs
+    # 2.5 ms); the composed path materialises fp32 L x L matrices, so long sequences always take the fused flash kernels (scores recomputed tile
+    # by tile, any sequence length).  Measured on MI355X (tools/cmp_attention_backward.py, profiles/r03_attention_backward_paths.txt).
+    return tokens > ATTENTION_BWD_MAX_TOKENS or not (pairs <= 2 and tokens >= 2048)
+
+
+_ATTENTION_BWD_ROUTES = ((_route_fused, "fused"), (_route_wide, "composed"), (_route_bf16, "bf16"), (_route_flash, "flash"), (lambda *shape: True, "composed"))
+
+
+def attention_backward_route(dtype, b: int, heads: int, lq: int, lk: int, dh: int, fused: bool = True):
+    """-> (route, dh_padded): which kernels differentiate attention over (b, lq | lk, heads * dh) operands of `dtype` -- "fused"
+    (ops.attention_backward_fused), "bf16" (ops.attention_backward_bf16), "flash" (ops.attention_backward) or "composed"
+    (_attention_backward_composed) -- by the table above.  dh_padded != dh: a head dim the flash / bf16 kernels are not built for, every head
+    is zero-padded to that width first (never for "fused", whose head dims are built ones).  fused=False: the routes that remain when the
+    library declines the fused kernels.  Plain integers and a dtype, no tensors, no library.  Raises ValueError for heads wider than the built
+    kernels beyond ATTENTION_BWD_MAX_TOKENS."""
+    widest = max(ops.ATTENTION_BWD_HEAD_DIMS)  # (= gm_attention_max_head_dim(): tests/test_attention_routes.py)
+    dhp = dh if dh > widest or dh in ops.ATTENTION_BWD_HEAD_DIMS else min(d for d in ops.ATTENTION_BWD_HEAD_DIMS if d >= dh)
+    shape = (dtype == torch.bfloat16, b * heads, max(lq, lk), dh, dhp)
+    for serves, route in _ATTENTION_BWD_ROUTES[0 if fused else 1:]:
+        if serves(*shape):
+            break
+    if dh > widest and max(lq, lk) > ATTENTION_BWD_MAX_TOKENS:
+        raise ValueError(f"attention backward with head dim {dh} (> {widest}) is limited to "
+                         f"{ATTENTION_BWD_MAX_TOKENS} tokens per side (got {lq} queries x {lk} keys)")
+    return route, dhp
 
 
 def _fused_backward_serves(q, k, heads):
+    """Whether the first row of the route table takes these operands (the forward keeps its log-sum-exp for the fused backward then)."""
     dh = q.shape[2] // heads
-    return (q.dtype == torch.bfloat16 and dh in ops.ATTENTION_BWD_FUSED_HEAD_DIMS and q.shape[2] == heads * dh
-            and max(q.shape[1], k.shape[1]) >= ATTENTION_BWD_FUSED_MIN_TOKENS)
+    return q.shape[2] == heads * dh and _route_fused(q.dtype == torch.bfloat16, q.shape[0] * heads, max(q.shape[1], k.shape[1]), dh, dh)
 
 
 class _Attention(torch.autograd.Function):
@@ -434,67 +486,42 @@ class _Attention(torch.autograd.Function):
     def backward(ctx, go):
         q, k, v, o, *rest = ctx.saved_tensors
         heads, scale = ctx.cfg
-        dh = q.shape[2] // heads
-        go = go.contiguous()
-        if _fused_backward_serves(q, k, heads):
-            grads = ops.attention_backward_fused(q, k, v, o, go, heads, scale, lse=rest[0] if rest else None, or_none=True)
-            if grads is not None:  # (None: the library declined -- more than 65 535 (sample, head) pairs, very wide rows: the round-4 path serves those)
-                return (*grads, None, None)
-        if dh in ops.ATTENTION_BWD_HEAD_DIMS:
-            return (*_attention_backward(q, k, v, o, go, heads, scale), None, None)
-        if dh > ops.lib().gm_attention_max_head_dim():
-            return (*_attention_backward_wide(q, k, v, go, heads, scale), None, None)
-        # any other head dim (<= 256): zero-pad every head to the next width the kernels are built for.  Zero channels add
-        # nothing to q k^T, and v's zero channels give o / dO zero channels: the products are unchanged, the padded gradient channels are dropped.
-        dhp = min(d for d in ops.ATTENTION_BWD_HEAD_DIMS if d >= dh)
-
-        def pad(t):
-            out = torch.zeros((t.shape[0], t.shape[1], heads * dhp), dtype=t.dtype, device=t.device)
-            for hi in range(heads):
-                ops.copy_channels(t[:, :, hi * dh:(hi + 1) * dh], out[:, :, hi * dhp:hi * dhp + dh])
-            return out
-
-        def unpad(t):
-            out = torch.empty((t.shape[0], t.shape[1], heads * dh), dtype=t.dtype, device=t.device)
-            for hi in range(heads):
-                ops.copy_channels(t[:, :, hi * dhp:hi * dhp + dh], out[:, :, hi * dh:(hi + 1) * dh])
-            return out
-
-        dq, dk, dv = _attention_backward(pad(q), pad(k), pad(v), pad(o), pad(go), heads, scale)
-        return unpad(dq), unpad(dk), unpad(dv), None, None
+        return (*attention_backward_by_route(q, k, v, o, go.contiguous(), heads, scale, lse=rest[0] if rest else None), None, None)
 
 
-def _attention_backward(q, k, v, o, go, heads, scale):
-    """(dq, dk, dv) for a head dim in ops.ATTENTION_BWD_HEAD_DIMS: which kernels, measured on MI355X (tools/cmp_attention_backward.py,
-    profiles/r03_attention_backward_paths.txt).  Every branch handles any sequence length: nothing raises for size."""
+def attention_backward_by_route(q, k, v, o, go, heads, scale, lse=None, route=None):
+    """(dq, dk, dv) of o = softmax(scale q k^T) v over (B, L, heads * dh) operands: route (attention_backward_route), pad the heads if the route
+    wants another width, dispatch, unpad.  lse: the forward kernel's log-sum-exp, for the fused kernels.  route: force one of the four (A/B
+    measurements: tools/) at the operands' own head dim -- its entry point raises when it does not serve them."""
     b, lq, c = q.shape
-    lk = k.shape[1]
-    dh = c // heads
-    long_seq = max(lq, lk) > ATTENTION_BWD_MAX_TOKENS
-    # bf16 operands on the bf16-MFMA score pass + the weight-gradient kernel (ops.attention_backward_bf16: every product at the bf16 MFMA rate;
-    # P, dS, dS^T of the (sample, head) pairs in flight live in HBM, one pair at a time when all of them would not fit): one or two pairs of
-    # >= 512 tokens (C4: one head x 4096 tokens at 16^3, one x 512 at 8^3) -- and ANY number of pairs above 8 192 tokens, where the fused fp32
-    # kernels below run at 45 TFLOP/s (84.6 ms per head at 32 768 x 256 against 16-17 ms here)
-    if (q.dtype == torch.bfloat16 and dh in ops.ATTENTION_BWD_BF16_HEAD_DIMS and max(lq, lk) >= ATTENTION_BWD_BF16_MIN_TOKENS
-            and (b * heads <= 2 or long_seq)):  # (any size: pairs beyond ops.ATTENTION_BWD_BF16_SLAB_BYTES of score matrices go through in query slabs)
-        return ops.attention_backward_bf16(q, k, v, o, go, heads, scale)
-    # fp32 (or bf16 below the bounds above): the fused kernels own 64 rows per work-group, so ONE head of a few thousand tokens leaves most CUs
-    # idle (L = 4096, d = 128: 1.9 ms fused vs 0.86 ms composed) while many (sample, head) pairs favour them (2 x 4 heads of 1024 tokens: 0.21 vs
-    # 2.5 ms); the composed path materialises fp32 L x L matrices, so long sequences always take the fused flash kernels
-    if long_seq or not (b * heads <= 2 and max(lq, lk) >= 2048):
-        return ops.attention_backward(q, k, v, o, go, heads, scale)  # fused flash backward: scores recomputed tile by tile, any sequence length
-    return _attention_backward_composed(q, k, v, go, heads, scale)
+    lk, dh = k.shape[1], c // heads
+    forced, dhp = route is not None, dh
+    if not forced:
+        route, dhp = attention_backward_route(q.dtype, b, heads, lq, lk, dh)
+    if route == "fused":
+        grads = ops.attention_backward_fused(q, k, v, o, go, heads, scale, lse=lse, or_none=not forced)
+        if grads is not None:
+            return grads
+        # the library declined (more than 65 535 (sample, head) pairs, very wide rows): the remaining routes serve those
+        route, dhp = attention_backward_route(q.dtype, b, heads, lq, lk, dh, fused=False)
 
+    # zero channels add nothing to q k^T, and v's zero channels give o / dO zero channels: the products are unchanged, the padded gradient
+    # channels are dropped
+    def widen(t, w0, w1):  # every head of t from w0 to w1 channels (the first min(w0, w1) are kept)
+        out = (torch.zeros if w1 > w0 else torch.empty)((t.shape[0], t.shape[1], heads * w1), dtype=t.dtype, device=t.device)
+        for hi in range(heads):
+            ops.copy_channels(t[:, :, hi * w0:hi * w0 + min(w0, w1)], out[:, :, hi * w1:hi * w1 + min(w0, w1)])
+        return out
 
-def _attention_backward_wide(q, k, v, go, heads, scale):
-    """(dq, dk, dv) for head dims above the fused backward kernels' 256 (the forward's sliced wide-head kernel): the composed per-(sample, head)
-    fp32 path, unpadded -- its GEMM / weight-gradient / softmax kernels take any head dim -- up to ATTENTION_BWD_MAX_TOKENS per side (it
-    materialises the fp32 Lq x Lk score matrices)."""
-    lq, lk = q.shape[1], k.shape[1]
-    if max(lq, lk) > ATTENTION_BWD_MAX_TOKENS:
-        raise ValueError(f"attention backward with head dim {q.shape[2] // heads} (> {ops.lib().gm_attention_max_head_dim()}) is limited to "
-                         f"{ATTENTION_BWD_MAX_TOKENS} tokens per side (got {lq} queries x {lk} keys)")
-    return _attention_backward_composed(q, k, v, go, heads, scale)
+    if dhp != dh:
+        q, k, v, o, go = (widen(t, dh, dhp) for t in (q, k, v, o, go))
+    if route == "composed":
+        grads = _attention_backward_composed(q, k, v, go, heads, scale)
+    elif route in ("bf16", "flash"):
+        grads = (ops.attention_backward_bf16 if route == "bf16" else ops.attention_backward)(q, k, v, o, go, heads, scale)
+    else:
+        raise ValueError(f"attention backward route {route!r} is none of 'fused', 'bf16', 'flash', 'composed'")
+    return grads if dhp == dh else tuple(widen(g, dhp, dh) for g in grads)
 
 
 def _attention_backward_composed(q, k, v, go, heads, scale):

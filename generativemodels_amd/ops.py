@@ -1723,30 +1723,58 @@ def gn_backward(x: torch.Tensor, gy: torch.Tensor, scale: torch.Tensor, shift: t
 ATTENTION_BWD_HEAD_DIMS = (16, 32, 64, 128, 256)
 
 
+def _attn_bwd_dims(q, k, v, o, go, heads: int):
+    """(B, Lq, Lk, dh) of the operands of an attention backward, which must agree in their shapes."""
+    b, lq, c = q.shape
+    if o.shape != q.shape or go.shape != q.shape or k.shape != v.shape or k.shape[2] != c:
+        raise ValueError("attention_backward operand shapes are inconsistent")
+    return b, lq, k.shape[1], c // heads
+
+
+def _attn_bwd_desc(q, k, v, o, go, heads: int, scale: float, *, grads=None, sample0: int = 0, samples: Optional[int] = None, head0: int = 0,
+                   nheads: Optional[int] = None, row0: int = 0, rows: Optional[int] = None) -> GmAttnBwdDesc:
+    """The descriptor of an attention backward over `samples` samples from sample0, `nheads` heads from head0 and `rows` query rows from row0 of
+    batch-dense (B, L, heads * dh) operands (default: all of them); grads = (dq, dk, dv) where the kernel writes them.  No workspace yet."""
+    b, lq, lk, dh = _attn_bwd_dims(q, k, v, o, go, heads)
+    d = GmAttnBwdDesc()
+    named = (("q", q, row0), ("k", k, 0), ("v", v, 0), ("o", o, row0), ("go", go, row0))
+    if grads is not None:
+        named += (("dq", grads[0], row0), ("dk", grads[1], 0), ("dv", grads[2], 0))
+    lds = [_kv_ld(t) for _, t, _ in named]
+    es = q.element_size()
+    for (name, t, r0), ld in zip(named, lds):
+        setattr(d, name, t.data_ptr() + (sample0 * t.stride(0) + r0 * ld + head0 * dh) * es)
+        setattr(d, name + "_ld", ld)
+        if name in ("q", "k", "v", "o", "go") and t.shape[0] > 1 and t.stride(0) != t.shape[1] * ld:
+            raise ValueError("attention_backward operands must be batch-dense")
+    d.B, d.H, d.Lq = b if samples is None else samples, heads if nheads is None else nheads, lq if rows is None else rows
+    d.Lk, d.dh = lk, dh
+    d.scale, d.dtype = float(scale), dt_code(q.dtype)
+    return d
+
+
+def _attn_bwd_workspace(d: GmAttnBwdDesc, planner: str, device, may_decline: bool = False) -> Optional[torch.Tensor]:
+    """Attaches the scratch the named gm_*_workspace_bytes planner asks for and returns it (the caller keeps it until the launch is enqueued);
+    may_decline: the planner answers 0 for operands its kernels do not serve -- nothing is attached then, and None returned."""
+    nbytes = getattr(lib(), planner)(C.byref(d))
+    if may_decline and nbytes <= 0:
+        return None
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+    return ws
+
+
 def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, go: torch.Tensor, heads: int, scale: float):
     """(dq, dk, dv) of o = softmax(scale q k^T) v per (batch, head) by the fused flash backward (gm_attention_backward): the scores are
     recomputed tile by tile, nothing L x L is stored.  (B, L, heads * dh) operands (channel slices allowed), dh in ATTENTION_BWD_HEAD_DIMS."""
     require_device(q, k, v, o, go)
-    b, lq, c = q.shape
-    lk = k.shape[1]
-    dh = c // heads
+    dh = q.shape[2] // heads
     if dh not in ATTENTION_BWD_HEAD_DIMS:
         raise ValueError(f"attention_backward: head dim {dh} not in {ATTENTION_BWD_HEAD_DIMS}")
-    if o.shape != q.shape or go.shape != q.shape or k.shape != v.shape or k.shape[2] != c:
-        raise ValueError("attention_backward operand shapes are inconsistent")
     dq, dk, dv = torch.empty_like(q.contiguous()), torch.empty_like(k.contiguous()), torch.empty_like(v.contiguous())
-    d = GmAttnBwdDesc()
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", o), ("go", go), ("dq", dq), ("dk", dk), ("dv", dv)):
-        setattr(d, name, t.data_ptr())
-        setattr(d, name + "_ld", _kv_ld(t))
-    for t, l in ((q, lq), (o, lq), (go, lq), (k, lk), (v, lk)):
-        if t.shape[0] > 1 and t.stride(0) != l * _kv_ld(t):
-            raise ValueError("attention_backward operands must be batch-dense")
-    d.B, d.H, d.Lq, d.Lk, d.dh = b, heads, lq, lk, dh
-    d.scale, d.dtype = float(scale), dt_code(q.dtype)
-    nbytes = lib().gm_attention_backward_workspace_bytes(C.byref(d))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+    d = _attn_bwd_desc(q, k, v, o, go, heads, scale, grads=(dq, dk, dv))
+    b, lq, lk = d.B, d.Lq, d.Lk
+    ws = _attn_bwd_workspace(d, "gm_attention_backward_workspace_bytes", q.device)  # noqa: F841 -- alive until the launch is enqueued
     _timed(f"attention_bwd<{str(q.dtype).split('.')[-1]}>", dict(flops=14.0 * b * heads * lq * lk * dh, bytes=float(5 * q.element_size() * q.numel()),
                                                               shape=f"B{b} H{heads} L{lq}x{lk} d{dh}"),
            lambda: check(lib().gm_attention_backward(C.byref(d), _stream()), "gm_attention_backward"))
@@ -1763,23 +1791,15 @@ def attention_backward_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     dh in ATTENTION_BWD_FUSED_HEAD_DIMS; lse: optional fp32 (B, heads, Lq) log-sum-exp of the scaled scores (else one more sweep computes it).
     (reference: torch autograd through diffusion_model_unet.py:407-415)"""
     require_device(q, k, v, o, go)
-    b, lq, c = q.shape
-    lk = k.shape[1]
-    dh = c // heads
-    if q.dtype != torch.bfloat16 or dh not in ATTENTION_BWD_FUSED_HEAD_DIMS:
+    if q.dtype != torch.bfloat16 or q.shape[2] // heads not in ATTENTION_BWD_FUSED_HEAD_DIMS:
         raise ValueError(f"attention_backward_fused: bf16 operands with a head dim in {ATTENTION_BWD_FUSED_HEAD_DIMS}")
-    if o.shape != q.shape or go.shape != q.shape or k.shape != v.shape or k.shape[2] != c:
-        raise ValueError("attention_backward operand shapes are inconsistent")
     q, k, v, o, go = (t.contiguous() for t in (q, k, v, o, go))
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    d = GmAttnBwdDesc()
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", o), ("go", go), ("dq", dq), ("dk", dk), ("dv", dv)):
-        setattr(d, name, t.data_ptr())
-        setattr(d, name + "_ld", _kv_ld(t))
-    d.B, d.H, d.Lq, d.Lk, d.dh = b, heads, lq, lk, dh
-    d.scale, d.dtype = float(scale), dt_code(q.dtype)
-    nbytes = lib().gm_attention_backward_fused_workspace_bytes(C.byref(d))
-    if nbytes <= 0:  # the library's own eligibility test (abd_eligible) is the one place the decision is made: callers with another path ask with or_none
+    d = _attn_bwd_desc(q, k, v, o, go, heads, scale, grads=(dq, dk, dv))
+    b, lq, lk, dh = d.B, d.Lq, d.Lk, d.dh
+    # the library's own eligibility test (abd_eligible) is the one place the decision is made: callers with another path ask with or_none
+    ws = _attn_bwd_workspace(d, "gm_attention_backward_fused_workspace_bytes", q.device, may_decline=True)
+    if ws is None:
         if or_none:
             return None
         raise ValueError("attention_backward_fused: operands not served by the fused bf16 kernels (alignment / size)")
@@ -1787,8 +1807,6 @@ def attention_backward_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
         if lse.dtype != torch.float32 or lse.numel() != b * heads * lq or not lse.is_contiguous():
             raise ValueError("attention_backward_fused: lse must be a contiguous fp32 (B, heads, Lq) tensor")
         require_device(lse)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
     _timed("attention_bwd_fused<bfloat16>", dict(flops=(14.0 if lse is not None else 16.0) * b * heads * lq * lk * dh, bytes=float(5 * 2 * q.numel()),
                                                  shape=f"B{b} H{heads} L{lq}x{lk} d{dh}"),
            lambda: check(lib().gm_attention_backward_fused(C.byref(d), lse.data_ptr() if lse is not None else None, _stream()), "gm_attention_backward_fused"))
@@ -1803,117 +1821,61 @@ ATTENTION_BWD_BF16_MAX_BYTES = 16 << 30  # the P and dS matrices of one call (2 
 ATTENTION_BWD_BF16_SLAB_BYTES = 512 << 20
 
 
+def _attn_bwd_bf16_plan(b: int, heads: int, lq: int, lk: int):
+    """(pairs per score pass, query rows per slab) of attention_backward_bf16, from the shapes and the two byte bounds alone: all B x H (sample,
+    head) pairs in one score pass when their matrices fit ATTENTION_BWD_BF16_MAX_BYTES, else one pair at a time through ONE set of buffers
+    (round 4: any batch x heads at any length -- 8 heads of 32 768 tokens re-use 6.4 GB instead of asking for 51 GB); a pair beyond
+    ATTENTION_BWD_BF16_SLAB_BYTES in slabs of query rows (a multiple of 64: 3 matrices x 2 bytes x Lk per row), any other in one slab of Lq rows."""
+    lkp, lqp = (lk + 63) // 64 * 64, (lq + 63) // 64 * 64
+    pair_bytes = (2 * lq * lkp + lkp * lqp) * 2  # P, dS [Lq][Lk] and dS^T [Lk][Lq] of ONE (sample, head) pair
+    if pair_bytes > ATTENTION_BWD_BF16_SLAB_BYTES and lq > 64:
+        return 1, max(64, int(ATTENTION_BWD_BF16_SLAB_BYTES // (6 * lkp)) // 64 * 64)
+    if pair_bytes > ATTENTION_BWD_BF16_MAX_BYTES:
+        raise ValueError("attention_backward_bf16: the score matrices of one (sample, head) pair exceed ATTENTION_BWD_BF16_MAX_BYTES")
+    return (b * heads if b * heads * pair_bytes <= ATTENTION_BWD_BF16_MAX_BYTES else 1), lq
+
+
 def attention_backward_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, go: torch.Tensor, heads: int, scale: float):
     """(dq, dk, dv) of o = softmax(scale q k^T) v with every product on the bf16 MFMA path (fp32 accumulation, fp32 softmax state):
     gm_attention_bwd_scores leaves P and dS as bf16 [Lq][Lk] matrices per (sample, head); dV = P^T dO and dK = dS^T Q run on the
     weight-gradient kernel (a contraction over rows: its transposed operand staging and its split over rows exist already), and so does
-    dQ = dS K = (dS^T)^T K, a contraction over the keys, from the dS^T image the score pass writes as well.
+    dQ = dS K = (dS^T)^T K, a contraction over the keys, from the dS^T image the score pass writes as well.  The score pass is row-wise in the
+    queries (LSE over all keys), so a slab of query rows is the same call on a row range of q / o / dO: dV = sum over slabs P_s^T dO_s and
+    dK = sum dS_s^T Q_s accumulate in fp32 in a fixed slab order (deterministic), dQ_s = dS_s K lands in its rows (_attn_bwd_bf16_plan).
     bf16 (B, L, heads * dh) operands, dh in ATTENTION_BWD_BF16_HEAD_DIMS.  (reference: torch autograd through diffusion_model_unet.py:407-415)"""
     require_device(q, k, v, o, go)
-    b, lq, c = q.shape
-    lk = k.shape[1]
-    dh = c // heads
-    if q.dtype != torch.bfloat16 or dh not in ATTENTION_BWD_BF16_HEAD_DIMS:
+    if q.dtype != torch.bfloat16 or q.shape[2] // heads not in ATTENTION_BWD_BF16_HEAD_DIMS:
         raise ValueError(f"attention_backward_bf16: bf16 operands with a head dim in {ATTENTION_BWD_BF16_HEAD_DIMS}")
-    if o.shape != q.shape or go.shape != q.shape or k.shape != v.shape or k.shape[2] != c:
-        raise ValueError("attention_backward operand shapes are inconsistent")
+    b, lq, lk, dh = _attn_bwd_dims(q, k, v, o, go, heads)
     q, k, v, o, go = (t.contiguous() for t in (q, k, v, o, go))
-    lkp, lqp = (lk + 63) // 64 * 64, (lq + 63) // 64 * 64
-    pair_bytes = (2 * lq * lkp + lkp * lqp) * 2  # P, dS [Lq][Lk] and dS^T [Lk][Lq] of ONE (sample, head) pair
-    if pair_bytes > ATTENTION_BWD_BF16_SLAB_BYTES and lq > 64:
-        return _attention_backward_bf16_slabs(q, k, v, o, go, heads, scale)
-    if pair_bytes > ATTENTION_BWD_BF16_MAX_BYTES:
-        raise ValueError("attention_backward_bf16: the score matrices of one (sample, head) pair exceed ATTENTION_BWD_BF16_MAX_BYTES")
-    # (sample, head) pairs per score pass: all of them when their matrices fit the scratch bound, else one at a time through ONE set of buffers
-    # (round 4: any batch x heads at any length -- 8 heads of 32 768 tokens re-use 6.4 GB instead of asking for 51 GB)
-    whole = b * heads * pair_bytes <= ATTENTION_BWD_BF16_MAX_BYTES
-    npairs = b * heads if whole else 1
-    probs = torch.empty((npairs, lq, lkp), dtype=torch.bfloat16, device=q.device)
+    npairs, slab = _attn_bwd_bf16_plan(b, heads, lq, lk)
+    lkp, st_ld = (lk + 63) // 64 * 64, (slab + 63) // 64 * 64
+    probs = torch.empty((npairs, slab, lkp), dtype=torch.bfloat16, device=q.device)
     dscores = torch.empty_like(probs)
-    dscores_t = torch.empty((npairs, lkp, lqp), dtype=torch.bfloat16, device=q.device)
+    dscores_t = torch.empty((npairs, lkp, st_ld), dtype=torch.bfloat16, device=q.device)
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    es = q.element_size()
-
-    def score_pass(bi0, nb, hi0, nh):
-        d = GmAttnBwdDesc()
-        for name, t in (("q", q), ("k", k), ("v", v), ("o", o), ("go", go)):
-            setattr(d, name, t.data_ptr() + (bi0 * t.shape[1] * t.shape[2] + hi0 * dh) * es)
-            setattr(d, name + "_ld", _kv_ld(t))
-        d.B, d.H, d.Lq, d.Lk, d.dh = nb, nh, lq, lk, dh
-        d.scale, d.dtype = float(scale), dt_code(q.dtype)
-        nbytes = lib().gm_attention_bwd_scores_workspace_bytes(C.byref(d))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
-        _timed("attention_bwd_scores<bfloat16>", dict(flops=6.0 * nb * nh * lq * lk * dh, bytes=float(6 * nb * nh * lq * lkp), shape=f"B{nb} H{nh} L{lq}x{lk} d{dh}"),
-               lambda: check(lib().gm_attention_bwd_scores(C.byref(d), probs.data_ptr(), dscores.data_ptr(), lkp, dscores_t.data_ptr(), lqp, _stream()),
-                             "gm_attention_bwd_scores"))
-
-    def contractions(bi, hi, i):
-        sl = slice(hi * dh, (hi + 1) * dh)
-        dvh = conv_wgrad(go[bi:bi + 1, :, sl], probs[i:i + 1, :, :lk], 1, 1, 0)                # [lk, dh, 1] fp32 = P^T dO
-        dkh = conv_wgrad(q[bi:bi + 1, :, sl], dscores[i:i + 1, :, :lk], 1, 1, 0)               # [lk, dh, 1] fp32 = dS^T Q
-        dqh = conv_wgrad(k[bi:bi + 1, :, sl], dscores_t[i:i + 1, :lk, :lq], 1, 1, 0)           # [lq, dh, 1] fp32 = dS K (rows = keys)
-        copy_channels(dqh.reshape(1, lq, dh), dq[bi:bi + 1, :, sl])
-        copy_channels(dkh.reshape(1, lk, dh), dk[bi:bi + 1, :, sl])
-        copy_channels(dvh.reshape(1, lk, dh), dv[bi:bi + 1, :, sl])
-
-    if whole:
-        score_pass(0, b, 0, heads)
-        for bi in range(b):
-            for hi in range(heads):
-                contractions(bi, hi, bi * heads + hi)
-    else:
-        for bi in range(b):
-            for hi in range(heads):
-                score_pass(bi, 1, hi, 1)
-                contractions(bi, hi, 0)
-    return dq, dk, dv
-
-
-def _attention_backward_bf16_slabs(q, k, v, o, go, heads: int, scale: float):
-    """attention_backward_bf16 for (sample, head) pairs whose L x L score matrices exceed ATTENTION_BWD_BF16_SLAB_BYTES: the same kernels over slabs
-    of query rows.  The score pass (LSE over all keys, P, dS, dS^T) is row-wise in the queries, so a slab is the call on a row range of q / o / dO;
-    dV = sum over slabs P_s^T dO_s and dK = sum dS_s^T Q_s accumulate in fp32 in a fixed slab order (deterministic), dQ_s = dS_s K lands in its rows."""
-    b, lq, c = q.shape
-    lk = k.shape[1]
-    dh = c // heads
-    lkp = (lk + 63) // 64 * 64
-    bq = max(64, int(ATTENTION_BWD_BF16_SLAB_BYTES // (6 * lkp)) // 64 * 64)  # query rows per slab: 3 matrices x 2 bytes x lkp per row
-    bqp = bq
-    probs = torch.empty((1, bq, lkp), dtype=torch.bfloat16, device=q.device)
-    dscores = torch.empty_like(probs)
-    dscores_t = torch.empty((1, lkp, bqp), dtype=torch.bfloat16, device=q.device)
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    es = q.element_size()
-    for bi in range(b):
-        for hi in range(heads):
-            sl = slice(hi * dh, (hi + 1) * dh)
-            dv32 = torch.empty((lk, dh, 1), dtype=torch.float32, device=q.device)
-            dk32 = torch.empty((lk, dh, 1), dtype=torch.float32, device=q.device)
-            for si, i0 in enumerate(range(0, lq, bq)):
-                rows = min(bq, lq - i0)
-                d = GmAttnBwdDesc()
-                for name, t in (("q", q), ("o", o), ("go", go)):
-                    setattr(d, name, t.data_ptr() + ((bi * lq + i0) * c + hi * dh) * es)
-                    setattr(d, name + "_ld", _kv_ld(t))
-                for name, t in (("k", k), ("v", v)):
-                    setattr(d, name, t.data_ptr() + (bi * lk * c + hi * dh) * es)
-                    setattr(d, name + "_ld", _kv_ld(t))
-                d.B, d.H, d.Lq, d.Lk, d.dh = 1, 1, rows, lk, dh
-                d.scale, d.dtype = float(scale), dt_code(q.dtype)
-                nbytes = lib().gm_attention_bwd_scores_workspace_bytes(C.byref(d))
-                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-                d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
-                _timed("attention_bwd_scores<bfloat16>", dict(flops=6.0 * rows * lk * dh, bytes=float(6 * rows * lkp), shape=f"slab {rows}x{lk} d{dh}"),
-                       lambda d=d: check(lib().gm_attention_bwd_scores(C.byref(d), probs.data_ptr(), dscores.data_ptr(), lkp, dscores_t.data_ptr(), bqp, _stream()),
-                                         "gm_attention_bwd_scores"))
-                qs, gs = q[bi:bi + 1, i0:i0 + rows, sl], go[bi:bi + 1, i0:i0 + rows, sl]
-                conv_wgrad(gs, probs[:, :rows, :lk], 1, 1, 0, out=dv32, accumulate=si > 0)              # dV += P_s^T dO_s
-                conv_wgrad(qs, dscores[:, :rows, :lk], 1, 1, 0, out=dk32, accumulate=si > 0)            # dK += dS_s^T Q_s
-                dqh = conv_wgrad(k[bi:bi + 1, :, sl], dscores_t[:, :lk, :rows], 1, 1, 0)               # [rows, dh, 1] = dS_s K
-                copy_channels(dqh.reshape(1, rows, dh), dq[bi:bi + 1, i0:i0 + rows, sl])
-            copy_channels(dk32.reshape(1, lk, dh), dk[bi:bi + 1, :, sl])
-            copy_channels(dv32.reshape(1, lk, dh), dv[bi:bi + 1, :, sl])
+    for p0 in range(0, b * heads, npairs):
+        nb, nh = (b, heads) if npairs > 1 else (1, 1)
+        # several slabs (of one pair): dV and dK accumulate over them in these; one slab: the contractions allocate their results
+        dv32, dk32 = (torch.empty((lk, dh, 1), dtype=torch.float32, device=q.device) for _ in range(2)) if slab < lq else (None, None)
+        for si, row0 in enumerate(range(0, lq, slab)):
+            rows = min(slab, lq - row0)
+            d = _attn_bwd_desc(q, k, v, o, go, heads, scale, sample0=p0 // heads, samples=nb, head0=p0 % heads, nheads=nh, row0=row0, rows=rows)
+            ws = _attn_bwd_workspace(d, "gm_attention_bwd_scores_workspace_bytes", q.device)  # noqa: F841 -- alive until the launch is enqueued
+            _timed("attention_bwd_scores<bfloat16>", dict(flops=6.0 * nb * nh * rows * lk * dh, bytes=float(6 * nb * nh * rows * lkp), shape=f"B{nb} H{nh} L{rows}x{lk} d{dh}"),
+                   lambda: check(lib().gm_attention_bwd_scores(C.byref(d), probs.data_ptr(), dscores.data_ptr(), lkp, dscores_t.data_ptr(), st_ld, _stream()),
+                                 "gm_attention_bwd_scores"))
+            for i in range(npairs):
+                bi, hi = divmod(p0 + i, heads)
+                sl = slice(hi * dh, (hi + 1) * dh)
+                qs, gs = q[bi:bi + 1, row0:row0 + rows, sl], go[bi:bi + 1, row0:row0 + rows, sl]
+                dvh = conv_wgrad(gs, probs[i:i + 1, :rows, :lk], 1, 1, 0, out=dv32, accumulate=si > 0)       # [lk, dh, 1] fp32: dV += P_s^T dO_s
+                dkh = conv_wgrad(qs, dscores[i:i + 1, :rows, :lk], 1, 1, 0, out=dk32, accumulate=si > 0)     # [lk, dh, 1] fp32: dK += dS_s^T Q_s
+                dqh = conv_wgrad(k[bi:bi + 1, :, sl], dscores_t[i:i + 1, :lk, :rows], 1, 1, 0)                # [rows, dh, 1] fp32 = dS_s K (rows = keys)
+                copy_channels(dqh.reshape(1, rows, dh), dq[bi:bi + 1, row0:row0 + rows, sl])
+                if row0 + rows == lq:
+                    copy_channels(dkh.reshape(1, lk, dh), dk[bi:bi + 1, :, sl])
+                    copy_channels(dvh.reshape(1, lk, dh), dv[bi:bi + 1, :, sl])
     return dq, dk, dv
 
 
@@ -1975,17 +1937,34 @@ def _kv_ld(t: torch.Tensor) -> int:
     return t.stride(1) if t.shape[1] > 1 else max(t.stride(1), t.shape[2])
 
 
+def _attn_desc(q, k, v, heads: int, o, scale: float = 1.0, res: Optional[torch.Tensor] = None, causal: bool = False) -> GmAttnDesc:
+    """The operands and the geometry of an attention forward into `o`; workspace, V image, LSE and statistics stay unset (NULL / 0)."""
+    b, lq, c = q.shape
+    lk = k.shape[1]
+    d = GmAttnDesc()
+    d.q, d.q_ld = q.data_ptr(), arena_ld(q)
+    d.k, d.k_ld = k.data_ptr(), _kv_ld(k)
+    d.v, d.v_ld = v.data_ptr(), _kv_ld(v)
+    if res is not None:
+        if tuple(res.shape) != (b, lq, c) or res.dtype != q.dtype:
+            raise ValueError("attention residual shape/dtype mismatch")
+        d.res, d.res_ld = res.data_ptr(), arena_ld(res)
+    d.o, d.o_ld = o.data_ptr(), arena_ld(o)
+    d.B, d.H, d.Lq, d.Lk, d.dh = b, heads, lq, lk, c // heads
+    d.scale, d.dtype = float(scale), dt_code(q.dtype)
+    d.causal = int(bool(causal))
+    # k / v may carry their own batch stride (the first Lk rows of a per-sample KV cache)
+    d.k_bs = k.stride(0) if (b > 1 and k.stride(0) != lk * d.k_ld) else 0
+    d.v_bs = v.stride(0) if (b > 1 and v.stride(0) != lk * d.v_ld) else 0
+    return d
+
+
 def attention_workspace(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, bytes_only: bool = False):
     """The scratch the LDS-DMA attention kernel wants for these operands (its transposed V image comes first), or None when another kernel
     serves the geometry.  An attention block allocates it BEFORE its q | k | v projection so that the projection can store the V image itself
     (conv(..., vt=(workspace, first V channel, head dim))) and passes it on: attention(..., workspace=ws, vt_packed=True)."""
-    b, lq, c = q.shape
-    d = GmAttnDesc()
-    d.q, d.q_ld, d.k, d.k_ld, d.v, d.v_ld = q.data_ptr(), arena_ld(q), k.data_ptr(), _kv_ld(k), v.data_ptr(), _kv_ld(v)
-    d.res, d.res_ld, d.o, d.o_ld = None, 0, q.data_ptr(), arena_ld(q)
-    d.B, d.H, d.Lq, d.Lk, d.dh, d.scale, d.dtype = b, heads, lq, k.shape[1], c // heads, 1.0, dt_code(q.dtype)
-    d.causal, d.k_bs, d.v_bs = 0, 0, 0
-    if b > 1 and (k.stride(0) != k.shape[1] * _kv_ld(k) or v.stride(0) != v.shape[1] * _kv_ld(v)):
+    d = _attn_desc(q, k, v, heads, q)  # (the output is not there yet: one as aligned as the queries)
+    if d.B > 1 and (k.stride(0) != d.Lk * d.k_ld or v.stride(0) != d.Lk * d.v_ld):  # a KV cache: another kernel
         return None
     nbytes = lib().gm_attention_workspace_bytes(C.byref(d))
     if bytes_only:
@@ -2015,26 +1994,11 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
         raise ValueError(f"head dim {dh} exceeds the gfx950 attention kernel limit ({lib().gm_attention_max_wide_head_dim()})")
     if out is None:
         out = torch.empty((b, lq, c), dtype=q.dtype, device=q.device)
-    d = GmAttnDesc()
-    d.q, d.q_ld = q.data_ptr(), arena_ld(q)
-    d.k, d.k_ld = k.data_ptr(), _kv_ld(k)
-    d.v, d.v_ld = v.data_ptr(), _kv_ld(v)
-    if res is not None:
-        if tuple(res.shape) != (b, lq, c) or res.dtype != q.dtype:
-            raise ValueError("attention residual shape/dtype mismatch")
-        d.res, d.res_ld = res.data_ptr(), arena_ld(res)
-    else:
-        d.res, d.res_ld = None, 0
-    d.o, d.o_ld = out.data_ptr(), arena_ld(out)
-    d.B, d.H, d.Lq, d.Lk, d.dh = b, heads, lq, lk, dh
-    d.scale, d.dtype = float(scale), dt_code(q.dtype)
+    d = _attn_desc(q, k, v, heads, out, scale, res, causal)
     # q / out / res: batch strides must equal L * ld (tokens of one sample are row-dense); k / v may carry their own batch stride
     for t, L in ((q, lq), (out, lq)) + (((res, lq),) if res is not None else ()):
         if t.shape[0] > 1 and t.stride(0) != L * arena_ld(t):
             raise ValueError("attention queries / outputs must be row-dense over (batch, tokens)")
-    d.causal = int(bool(causal))
-    d.k_bs = k.stride(0) if (b > 1 and k.stride(0) != lk * _kv_ld(k)) else 0
-    d.v_bs = v.stride(0) if (b > 1 and v.stride(0) != lk * _kv_ld(v)) else 0
     if causal and lk < lq:
         raise ValueError("causal attention needs at least as many keys as queries")
     d.workspace, d.workspace_bytes = None, 0

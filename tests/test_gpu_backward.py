@@ -1234,12 +1234,14 @@ def test_attention_backward_bf16_in_query_slabs(monkeypatch, b, lq, lk, heads, d
     o = ops.attention(qd, kd, vd, heads, scale)
     whole = ops.attention_backward_bf16(qd, kd, vd, o, gd, heads, scale)
     lkp = (lk + 63) // 64 * 64
-    monkeypatch.setattr(ops, "ATTENTION_BWD_BF16_SLAB_BYTES", 6 * lkp * (128 if lq > 400 else 64))
-    calls = []
-    real = ops._attention_backward_bf16_slabs
-    monkeypatch.setattr(ops, "_attention_backward_bf16_slabs", lambda *a: (calls.append(1), real(*a))[1])
-    slabs = ops.attention_backward_bf16(qd, kd, vd, o, gd, heads, scale)
-    assert calls, "the slab path did not run"
+    slab_rows = 128 if lq > 400 else 64
+    monkeypatch.setattr(ops, "ATTENTION_BWD_BF16_SLAB_BYTES", 6 * lkp * slab_rows)
+    ops.start_profile()
+    try:
+        slabs = ops.attention_backward_bf16(qd, kd, vd, o, gd, heads, scale)
+    finally:
+        passes = sum(name.startswith("attention_bwd_scores") for name, _, _ in ops.stop_profile())
+    assert passes > b * heads and passes == b * heads * -(-lq // slab_rows), f"{passes} score passes: the slabs did not run"
     for name, got, w, r in zip("qkv", slabs, whole, ref):
         _close(got, r.grad, 1.5e-2, f"slabbed bf16-MFMA attention backward d{name}")
         _close(got, w.double().cpu(), 1e-2, f"slabbed vs whole-pair d{name}")

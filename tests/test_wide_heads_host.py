@@ -60,11 +60,13 @@ def test_wide_heads_train_through_the_composed_backward(dh, dtype, monkeypatch):
     q = torch.empty((1, 4096, heads * dh), dtype=dtype, device="meta")
     k = torch.empty((1, 300, heads * dh), dtype=dtype, device="meta")
     assert not A._fused_backward_serves(q, k, heads)
+    assert A.attention_backward_route(dtype, 1, heads, 4096, 300, dh) == ("composed", dh)  # not a fused / flash / bf16 route, and no padding
     seen = []
     monkeypatch.setattr(A, "_attention_backward_composed", lambda q_, k_, v_, go_, h_, s_: seen.append((tuple(q_.shape), h_)) or (q_, k_, v_))
-    monkeypatch.setattr(A, "_attention_backward", lambda *a: pytest.fail("a fused / padded route was taken"))
     grads = A._Attention.backward(_Ctx((q, k, k, q), heads), q)
     assert seen == [((1, 4096, heads * dh), heads)] and grads[3] is None and grads[4] is None
     long_q = torch.empty((1, A.ATTENTION_BWD_MAX_TOKENS + 1, heads * dh), dtype=dtype, device="meta")
+    with pytest.raises(ValueError, match=str(A.ATTENTION_BWD_MAX_TOKENS)):
+        A.attention_backward_route(dtype, 1, heads, A.ATTENTION_BWD_MAX_TOKENS + 1, 300, dh)
     with pytest.raises(ValueError, match=str(A.ATTENTION_BWD_MAX_TOKENS)):
         A._Attention.backward(_Ctx((long_q, k, k, long_q), heads), long_q)

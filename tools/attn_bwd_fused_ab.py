@@ -34,7 +34,8 @@ for shp in shapes:
     o = ops.attention(q, k, v, h, scale, lse_out=lse)
     tf, outf = timed(lambda: ops.attention_backward_fused(q, k, v, o, go, h, scale))
     tg, outg = timed(lambda: ops.attention_backward_fused(q, k, v, o, go, h, scale, lse=lse)) if lse is not None else (float("nan"), outf)
-    tc, outc = timed(lambda: A._attention_backward(q, k, v, o, go, h, scale))  # the round-4 policy
+    round4 = A.attention_backward_route(q.dtype, b, h, l, lk, dh, fused=False)[0]  # the round-4 policy: the routes without the fused kernels
+    tc, outc = timed(lambda: A.attention_backward_by_route(q, k, v, o, go, h, scale, route=round4))
     tfw, _ = timed(lambda: ops.attention(q, k, v, h, scale))
     tfl, _ = timed(lambda: ops.attention(q, k, v, h, scale, lse_out=lse)) if lse is not None else (float("nan"), None)
     err = max((a.float() - c.float()).abs().max().item() / max(1e-6, c.float().abs().max().item()) for a, c in zip(outg, outc))

@@ -1,7 +1,7 @@
 """GPU: the three attention-backward paths (ops.attention_backward = fused fp32-MFMA flash kernels; the fp32 composed path of autograd.py;
 ops.attention_backward_bf16 = bf16-MFMA score pass + weight-gradient / 1x1 kernels) at training shapes.   usage: python tools/cmp_attention_backward.py"""
 import sys, json, math, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, ".")
 from generativemodels_amd import ops, autograd as A
 def timeit(fn, reps=3, warm=1):
     for _ in range(warm): fn()
@@ -22,18 +22,7 @@ for b,l,h,dh in [(1,4096,1,128),(1,512,1,256),(1,8192,1,64),(2,1024,4,32),(1,327
     ops.start_profile(); ops.attention_backward_bf16(q,k,v,o,go,h,sc); rec=ops.stop_profile()
     parts={}
     for name,meta,ms in rec: parts[name]=round(parts.get(name,0.0)+ms,3)
-    t_c=None
-    if l <= 8192:
-        saved=(ops.ATTENTION_BWD_HEAD_DIMS, A.ATTENTION_BWD_BF16_MIN_TOKENS)
-        def composed():
-            ops.ATTENTION_BWD_HEAD_DIMS=(); A.ATTENTION_BWD_BF16_MIN_TOKENS=1<<30
-            qq,kk,vv=(t.clone().requires_grad_(True) for t in (q,k,v))
-            oo=A.attention(qq,kk,vv,h,sc); oo.backward(go)
-            ops.ATTENTION_BWD_HEAD_DIMS, A.ATTENTION_BWD_BF16_MIN_TOKENS=saved
-        def fwd_only():
-            qq,kk,vv=(t.clone().requires_grad_(True) for t in (q,k,v))
-            A.attention(qq,kk,vv,h,sc)
-        t_c=timeit(composed)-timeit(fwd_only)
+    t_c=timeit(lambda: A.attention_backward_by_route(q,k,v,o,go,h,sc,route="composed")) if l <= 8192 else None
     flops=10.0*b*h*l*l*dh
     print(json.dumps(dict(B=b,L=l,H=h,dh=dh,fused_fp32_ms=None if t_f is None else round(t_f,3),composed_fp32_ms=None if t_c is None else round(t_c,3),
                           bf16_mfma_ms=round(t_b,3),bf16_tflops_of_5_gemms=round(flops/t_b/1e9,1),bf16_parts_ms=parts)),flush=True)
