@@ -33,6 +33,8 @@ struct QkvAttnArgs {  // small_ops.hip
   float scale; float* ws; int chunk, sc_elems;
 };
 extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream);
+extern "C" int gm_qkv_attn_rows_plan(const QkvAttnArgs* ap, int dtype, int* ng, int* um);  // which instantiation would take it; launches nothing
+extern "C" int gm_linear_rows_takes_ksplit(int rows, int cin, int dtype);
 extern "C" int gm_linear_rows_kvmerge(const float* kv_ws, int kv_ns, int kv_dh, const void* w, const float* bias, const void* res, long long res_ld,
                                       void* y, long long y_ld, int rows, int cin, int cout, int dtype, void* stream);
 extern "C" int gm_layernorm(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta, long long rows,
@@ -91,28 +93,119 @@ static int linear_rows(const void* x, long long x_ld, const void* w, const float
   return gm_linear_rows(x, x_ld, w, b, res, res_ld, y, y_ld, rows, cin, cout, 0, post_act, dtype, stream);
 }
 
-extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) {
-  GM_REQUIRE(dp, "null descriptor");
-  const GmDecodeDesc& d = *dp;
-  GM_REQUIRE(d.tokens && d.tok_emb && d.pos_emb && d.blocks && d.w_logits && d.logits && d.scratch, "null pointer");
-  GM_REQUIRE(d.B > 0 && d.C > 0 && d.M > 0 && d.heads > 0 && d.C % d.heads == 0 && d.depth > 0, "bad geometry");
-  GM_REQUIRE(d.pos_dev || (d.pos >= 0 && d.pos < d.max_len), "position outside the context window");
-  const int hpos = d.pos_dev ? 0 : d.pos;  // host-side position (0 when the device supplies it)
-  GM_REQUIRE(d.scratch_bytes >= gm_decode_scratch_bytes(d.B, d.C, d.M, d.dtype), "scratch too small");
-  const long long es = elt(d.dtype);
-  auto r = [](long long v) { return (v + 255) / 256 * 256; };
-  char* s = reinterpret_cast<char*>(d.scratch);
-  char* x0 = s;  s += r((long long)d.B * d.C * es);
-  char* x1 = s;  s += r((long long)d.B * d.C * es);
-  char* h = s;   s += r((long long)d.B * d.C * es);
-  char* y = s;   s += r((long long)d.B * d.C * es);
-  char* qkv = s; s += r(3LL * d.B * d.C * es);
-  char* a = s;   s += r((long long)d.B * d.M * es);
-  float* kv_ws = reinterpret_cast<float*>(s); s += r((long long)d.B * DECODE_KV_SPLITS * 3 * d.C * 4);
-  float* mlp_p = reinterpret_cast<float*>(s);
+// (include/gm_amd.h: the GM_DECODE_PLAN_* indices and values; tests/test_decode_routes.py pins the plans through the header's names)
+enum {
+  GM_DECODE_PLAN_SPLIT_KV, GM_DECODE_PLAN_QKV_NG, GM_DECODE_PLAN_QKV_UM, GM_DECODE_PLAN_QKV_INPUT, GM_DECODE_PLAN_OUT_MERGE, GM_DECODE_PLAN_ATTN_ENTRY,
+  GM_DECODE_PLAN_MLP_FUSED, GM_DECODE_PLAN_KSPLIT_QKV, GM_DECODE_PLAN_KSPLIT_OUT, GM_DECODE_PLAN_KSPLIT_MLP_UP, GM_DECODE_PLAN_KSPLIT_MLP_DOWN,
+  GM_DECODE_PLAN_KSPLIT_LOGITS, GM_DECODE_PLAN_COUNT
+};
+enum { GM_DECODE_INPUT_ROW, GM_DECODE_INPUT_MLP_MERGE };
+enum { GM_DECODE_MERGE_NONE, GM_DECODE_MERGE_OUT_PROJ, GM_DECODE_MERGE_COMBINE };
+enum { GM_DECODE_ENTRY_NONE, GM_DECODE_ENTRY_HOST_POS, GM_DECODE_ENTRY_DEVICE_POS };
+
+// ---- the route plan ---------------------------------------------------------------------------------------------------------------------
+// Every route decision of the step, taken in ONE place: block `blk`'s routes (and the step-wide ones) as GM_DECODE_PLAN_COUNT ints, indexed
+// by the GM_DECODE_PLAN_* names of include/gm_amd.h.  gm_transformer_decode_step consults it per block; gm_transformer_decode_plan exports it.
+// The decisions depend on the geometry, the dtype, null-ness of pointers and host-or-device position only -- never on the position itself.
+static bool decode_mlp_fused(const GmDecodeDesc& d) {
   // the MLP as one launch leaving M / 64 K-slice partials that the next launch's prologue sums with the residual row (small_ops.hip)
   bool mlp_fuse = gm_mlp_rows_fusable(d.B, d.C, d.M, d.dtype) == 1;
   for (int i = 0; i < d.depth; ++i) mlp_fuse = mlp_fuse && d.blocks[i].ln3_g;  // (its staging pass is the LayerNorm)
+  return mlp_fuse;
+}
+
+// the fused q|k|v + attention kernel's arguments for block `blk` (everything but the position), as the step passes them
+static QkvAttnArgs decode_qkv_args(const GmDecodeDesc& d, int blk, bool mlp_fuse, char* x0, char* x1, float* mlp_p, float* kv_ws) {
+  const GmDecodeBlock& b = d.blocks[blk];
+  QkvAttnArgs qa = {};
+  if (mlp_fuse && blk > 0) { qa.mlp_p = mlp_p; qa.mlp_nj = d.M / 64; qa.mlp_x1 = x1; qa.mlp_b2 = d.blocks[blk - 1].b_2; qa.x0_out = x0; }
+  else qa.x0 = x0;
+  qa.ln_g = b.ln1_g; qa.ln_b = b.ln1_b; qa.ln_eps = d.ln_eps;
+  qa.w = b.w_qkv; qa.bias = b.b_qkv;
+  qa.kcache = b.k_cache; qa.vcache = b.v_cache;
+  qa.B = d.B; qa.H = d.heads; qa.C = d.C; qa.dh = d.C / d.heads; qa.cap = d.max_len; qa.pos_dev = d.pos_dev;
+  qa.scale = 1.0f / sqrtf((float)(d.C / d.heads)); qa.ws = kv_ws;
+  return qa;
+}
+
+static void decode_plan(const GmDecodeDesc& d, int blk, const QkvAttnArgs& qa, bool mlp_fuse, int* f) {
+  static const bool kv_split = !(getenv("GM_DECODE_KV_SPLIT") && getenv("GM_DECODE_KV_SPLIT")[0] == '0');  // bench switches (tools/diag_c5.py)
+  static const bool kv_fuse = !(getenv("GM_DECODE_KV_FUSE") && getenv("GM_DECODE_KV_FUSE")[0] == '0');
+  for (int i = 0; i < GM_DECODE_PLAN_COUNT; ++i) f[i] = 0;
+  const int dh = d.C / d.heads;
+  const bool split = kv_split && d.max_len > DECODE_SPLIT_MIN_LEN;
+  const bool ks_c = gm_linear_rows_takes_ksplit(d.B, d.C, d.dtype) == 1, ks_m = gm_linear_rows_takes_ksplit(d.B, d.M, d.dtype) == 1;
+  f[GM_DECODE_PLAN_SPLIT_KV] = split;
+  // LayerNorm + q | k | v + the attention ranges as one launch where that kernel takes the geometry (split windows only)
+  int ng = 0, um = 0;
+  const bool qkv_fused = split && gm_qkv_attn_rows_plan(&qa, d.dtype, &ng, &um) == 1;
+  f[GM_DECODE_PLAN_QKV_NG] = qkv_fused ? ng : 0;
+  f[GM_DECODE_PLAN_QKV_UM] = qkv_fused ? um : 0;
+  // behind a fused MLP the q|k|v launch (fused or GEMM) assembles its input from the previous block's partials
+  f[GM_DECODE_PLAN_QKV_INPUT] = mlp_fuse && blk > 0 ? GM_DECODE_INPUT_MLP_MERGE : GM_DECODE_INPUT_ROW;
+  // the partials are merged by the out-projection's prologue where its K-split kernel applies, by a combine launch otherwise: the two
+  // forms give the same bits, and which one runs depends on the geometry only
+  f[GM_DECODE_PLAN_OUT_MERGE] = !split ? GM_DECODE_MERGE_NONE
+                                : kv_fuse && dh % (d.dtype == GM_F32 ? 4 : 8) == 0 && d.C % dh == 0 && ks_c ? GM_DECODE_MERGE_OUT_PROJ : GM_DECODE_MERGE_COMBINE;
+  f[GM_DECODE_PLAN_ATTN_ENTRY] = split ? GM_DECODE_ENTRY_NONE : d.pos_dev ? GM_DECODE_ENTRY_DEVICE_POS : GM_DECODE_ENTRY_HOST_POS;
+  f[GM_DECODE_PLAN_MLP_FUSED] = mlp_fuse;
+  f[GM_DECODE_PLAN_KSPLIT_QKV] = !qkv_fused && ks_c;  // (the fused kernel replaces the GEMM)
+  f[GM_DECODE_PLAN_KSPLIT_OUT] = ks_c;
+  f[GM_DECODE_PLAN_KSPLIT_MLP_UP] = !mlp_fuse && ks_c;  // (the fused MLP kernel replaces both GEMMs)
+  f[GM_DECODE_PLAN_KSPLIT_MLP_DOWN] = !mlp_fuse && ks_m;
+  f[GM_DECODE_PLAN_KSPLIT_LOGITS] = ks_c;
+}
+
+// the descriptor checks shared by the step and its plan (a macro: a failure names the entry point that was called)
+#define GM_DECODE_CHECK(dp)                                                                                                               \
+  do {                                                                                                                                    \
+    GM_REQUIRE(dp, "null descriptor");                                                                                                    \
+    GM_REQUIRE(dp->tokens && dp->tok_emb && dp->pos_emb && dp->blocks && dp->w_logits && dp->logits && dp->scratch, "null pointer");      \
+    GM_REQUIRE(dp->B > 0 && dp->C > 0 && dp->M > 0 && dp->heads > 0 && dp->C % dp->heads == 0 && dp->depth > 0, "bad geometry");           \
+    GM_REQUIRE(dp->pos_dev || (dp->pos >= 0 && dp->pos < dp->max_len), "position outside the context window");                            \
+    GM_REQUIRE(dp->scratch_bytes >= gm_decode_scratch_bytes(dp->B, dp->C, dp->M, dp->dtype), "scratch too small");                        \
+  } while (0)
+
+struct DecodeScratch { char *x0, *x1, *h, *y, *qkv, *a; float *kv_ws, *mlp_p; };
+static DecodeScratch decode_scratch(const GmDecodeDesc& d) {
+  const long long es = elt(d.dtype);
+  auto r = [](long long v) { return (v + 255) / 256 * 256; };
+  DecodeScratch w;
+  char* s = reinterpret_cast<char*>(d.scratch);
+  w.x0 = s;  s += r((long long)d.B * d.C * es);
+  w.x1 = s;  s += r((long long)d.B * d.C * es);
+  w.h = s;   s += r((long long)d.B * d.C * es);
+  w.y = s;   s += r((long long)d.B * d.C * es);
+  w.qkv = s; s += r(3LL * d.B * d.C * es);
+  w.a = s;   s += r((long long)d.B * d.M * es);
+  w.kv_ws = reinterpret_cast<float*>(s); s += r((long long)d.B * DECODE_KV_SPLITS * 3 * d.C * 4);
+  w.mlp_p = reinterpret_cast<float*>(s);
+  return w;
+}
+
+// The plan of the step `dp` describes, launching nothing: flags[GM_DECODE_PLAN_COUNT].  The per-block entries are those of the last block
+// (with depth >= 2 that is the steady state: block 0 alone has no MLP partials in front of it and always takes the plain row).
+extern "C" int gm_transformer_decode_plan(const GmDecodeDesc* dp, int* flags) {
+  GM_REQUIRE(flags, "null pointer");
+  GM_DECODE_CHECK(dp);
+  const GmDecodeDesc& d = *dp;
+  const DecodeScratch w = decode_scratch(d);
+  const bool mlp_fuse = decode_mlp_fused(d);
+  const int blk = d.depth - 1;
+  const QkvAttnArgs qa = decode_qkv_args(d, blk, mlp_fuse, w.x0, w.x1, w.mlp_p, w.kv_ws);
+  decode_plan(d, blk, qa, mlp_fuse, flags);
+  return 0;
+}
+
+extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) {
+  GM_DECODE_CHECK(dp);
+  const GmDecodeDesc& d = *dp;
+  const int hpos = d.pos_dev ? 0 : d.pos;  // host-side position (0 when the device supplies it)
+  const long long es = elt(d.dtype);
+  const DecodeScratch w = decode_scratch(d);
+  char *x0 = w.x0, *x1 = w.x1, *y = w.y, *qkv = w.qkv, *a = w.a;
+  float *kv_ws = w.kv_ws, *mlp_p = w.mlp_p;
+  const bool mlp_fuse = decode_mlp_fused(d);
   const int mlp_nj = d.M / 64;
   const int C = d.C;
   int rc = gm_embed_tokens_dev(d.tokens, d.tok_emb, d.pos_emb, x0, d.B, 1, C, hpos, d.num_tokens, d.max_len, d.dtype, d.pos_dev, stream);
@@ -121,23 +214,18 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
   for (int i = 0; i < d.depth; ++i) {
     const GmDecodeBlock& b = d.blocks[i];
     GM_REQUIRE(b.w_qkv && b.w_o && b.w_1 && b.w_2 && b.k_cache && b.v_cache, "null block parameter");
-    static const bool kv_split = !(getenv("GM_DECODE_KV_SPLIT") && getenv("GM_DECODE_KV_SPLIT")[0] == '0');  // bench switches (tools/diag_c5.py)
-    static const bool kv_fuse = !(getenv("GM_DECODE_KV_FUSE") && getenv("GM_DECODE_KV_FUSE")[0] == '0');
-    const bool split = kv_split && d.max_len > DECODE_SPLIT_MIN_LEN;
+    QkvAttnArgs qa = decode_qkv_args(d, i, mlp_fuse, x0, x1, mlp_p, kv_ws);
+    int plan[GM_DECODE_PLAN_COUNT];
+    decode_plan(d, i, qa, mlp_fuse, plan);
+    const bool split = plan[GM_DECODE_PLAN_SPLIT_KV] != 0;
     // LayerNorm + q | k | v + the attention ranges as ONE launch where that kernel takes the geometry (small_ops.hip: qkv_attn_rows_kernel) ...
     bool qkv_done = false;
-    if (split) {
-      QkvAttnArgs qa = {};
-      if (mlp_fuse && i > 0) { qa.mlp_p = mlp_p; qa.mlp_nj = mlp_nj; qa.mlp_x1 = x1; qa.mlp_b2 = d.blocks[i - 1].b_2; qa.x0_out = x0; }
-      else qa.x0 = x0;
-      qa.ln_g = b.ln1_g; qa.ln_b = b.ln1_b; qa.ln_eps = d.ln_eps;
-      qa.w = b.w_qkv; qa.bias = b.b_qkv;
-      qa.kcache = b.k_cache; qa.vcache = b.v_cache;
-      qa.B = d.B; qa.H = d.heads; qa.C = C; qa.dh = C / d.heads; qa.cap = d.max_len; qa.pos = hpos; qa.pos_dev = d.pos_dev;
-      qa.scale = scale; qa.ws = kv_ws;
+    if (plan[GM_DECODE_PLAN_QKV_NG]) {
+      qa.pos = hpos;
       rc = gm_qkv_attn_rows(&qa, d.dtype, stream);
       if (rc < 0) return rc;
-      qkv_done = rc == 1;
+      GM_REQUIRE(rc == 1, "the fused q|k|v + attention launch disagrees with the plan");
+      qkv_done = true;
     }
     // ... otherwise LayerNorm + stacked q | k | v projection in one launch; the key / value rows land directly in cache row `pos` of every sequence.
     // Behind a fused MLP the launch first assembles its input x0 = x1 + b2 + sum_j P[j] (and stores it: the out-projection below adds it as the residual)
@@ -145,7 +233,7 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
     char* vdst = reinterpret_cast<char*>(b.v_cache) + (long long)hpos * C * es;
     if (qkv_done)
       rc = 0;
-    else if (mlp_fuse && i > 0)
+    else if (plan[GM_DECODE_PLAN_QKV_INPUT] == GM_DECODE_INPUT_MLP_MERGE)
       rc = gm_linear_rows_mlpmerge(mlp_p, mlp_nj, x1, d.blocks[i - 1].b_2, x0, b.ln1_g, b.ln1_b, d.ln_eps, b.w_qkv, b.b_qkv, qkv, 3 * C, kdst, vdst,
                                    (long long)d.max_len * C, C, d.B, C, 3 * C, 0, d.dtype, d.pos_dev, C, stream);
     else
@@ -163,14 +251,15 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
     if (split) {
       // the partials are merged by the out-projection's prologue where its K-split kernel applies, by a combine launch otherwise: the two
       // forms give the same bits, and which one runs depends on the geometry only
-      const bool fuse = kv_fuse && at.dh % (d.dtype == GM_F32 ? 4 : 8) == 0;
+      const bool fuse = plan[GM_DECODE_PLAN_OUT_MERGE] == GM_DECODE_MERGE_OUT_PROJ;
       if (!qkv_done)
         GM_REQUIRE(gm_attention_decode_split(&at, d.pos_dev, kv_ws, DECODE_KV_SPLITS, 0, d.max_len, stream) == 1, "head size beyond the single-query attention kernels");
       rc = fuse ? gm_linear_rows_kvmerge(kv_ws, DECODE_KV_SPLITS, at.dh, b.w_o, b.b_o, x0, C, x1, C, d.B, C, C, d.dtype, stream) : 0;
       if (rc < 0) return rc;
+      GM_REQUIRE((rc == 1) == fuse, "the partial-merging out-projection disagrees with the plan");
       out_done = rc == 1;
       if (!out_done) GM_REQUIRE(gm_attention_decode_split(&at, d.pos_dev, kv_ws, DECODE_KV_SPLITS, 2, d.max_len, stream) == 1, "merge of the attention partials");
-    } else if (d.pos_dev) {
+    } else if (plan[GM_DECODE_PLAN_ATTN_ENTRY] == GM_DECODE_ENTRY_DEVICE_POS) {
       GM_REQUIRE(gm_attention_decode_dev(&at, d.pos_dev, stream) == 1, "context window too long for the single-query attention kernel");
     } else if ((rc = gm_attention_forward(&at, stream))) {
       return rc;

@@ -1246,9 +1246,9 @@ __global__ __launch_bounds__(256) void qkv_attn_rows_kernel(QkvAttnArgs a) {
   attn_range_body<T>(K, C, V, C, k1 - k0, dh, qs, sc, red, wsp, wm, wl, tid);
 }
 
-// 1 = launched, 0 = not this kernel's case (the caller issues the LayerNorm + q|k|v GEMM and gm_attention_decode_split), < 0 = error.
-extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream) {
-  const QkvAttnArgs& a = *ap;
+// Which instantiation takes this geometry: 1 and (*ng, *um) = its template arguments (and the launch geometry in *chunk, *sc_elems, *smem when
+// given), 0 = none.  The one decision both the launch below and the decode step's plan (decode_step.hip) consult.
+static int qkv_attn_rows_select(const QkvAttnArgs& a, int dtype, int* ng_out, int* um_out, int* chunk_out, int* sc_out, size_t* smem_out) {
   static const bool on = !(getenv("GM_DECODE_QKV_FUSE") && getenv("GM_DECODE_QKV_FUSE")[0] == '0');  // bench switch (tools/diag_c5.py)
   if (!on || (dtype != GM_F32 && dtype != GM_BF16)) return 0;
   const int bk = dtype == GM_F32 ? 16 : 32, vecw = dtype == GM_F32 ? 4 : 8;
@@ -1258,10 +1258,34 @@ extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream) 
   const int chunk = ((a.cap + GM_DECODE_KV_SPLITS - 1) / GM_DECODE_KV_SPLITS + 63) & ~63;
   const int sc_elems = chunk > 256 * vecw ? chunk : 256 * vecw;
   if (sc_elems > 32768 || (long long)a.B * a.H > 65535) return 0;
-  QkvAttnArgs k = a;
-  k.chunk = chunk; k.sc_elems = sc_elems;
   const size_t smem = (size_t)(sc_elems + a.dh + 8 + a.C + 12 * a.dh) * sizeof(float) + (size_t)a.C * (dtype == GM_F32 ? 4 : 2);
   if (smem > 160 * 1024) return 0;
+  int sel_ng = 0, sel_um = 0;  // (the same table for both dtypes; first match wins)
+  if (ng == 6 && um <= 2) { sel_ng = 6; sel_um = 2; }
+  else if (ng == 6 && um <= 4) { sel_ng = 6; sel_um = 4; }
+  else if (ng == 12 && um <= 2) { sel_ng = 12; sel_um = 2; }
+  else return 0;
+  if (ng_out) *ng_out = sel_ng;
+  if (um_out) *um_out = sel_um;
+  if (chunk_out) *chunk_out = chunk;
+  if (sc_out) *sc_out = sc_elems;
+  if (smem_out) *smem_out = smem;
+  return 1;
+}
+// the non-launching query beside gm_qkv_attn_rows: 1 and the instantiation (NG, UM) that would take `ap`, or 0
+extern "C" int gm_qkv_attn_rows_plan(const QkvAttnArgs* ap, int dtype, int* ng, int* um) {
+  return qkv_attn_rows_select(*ap, dtype, ng, um, nullptr, nullptr, nullptr);
+}
+extern "C" int gm_linear_rows_takes_ksplit(int rows, int cin, int dtype) { return linear_rows_takes_ksplit(rows, cin, dtype) ? 1 : 0; }
+
+// 1 = launched, 0 = not this kernel's case (the caller issues the LayerNorm + q|k|v GEMM and gm_attention_decode_split), < 0 = error.
+extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream) {
+  const QkvAttnArgs& a = *ap;
+  int ng = 0, um = 0, chunk = 0, sc_elems = 0;
+  size_t smem = 0;
+  if (!qkv_attn_rows_select(a, dtype, &ng, &um, &chunk, &sc_elems, &smem)) return 0;
+  QkvAttnArgs k = a;
+  k.chunk = chunk; k.sc_elems = sc_elems;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(a.B * a.H, GM_DECODE_KV_SPLITS);
 #define GM_QKV_LAUNCH(T, NG, UM)                                                                                          \
@@ -1275,13 +1299,13 @@ extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream) 
     return hipGetLastError() == hipSuccess ? 1 : -1;                                                                      \
   } while (0)
   if (dtype == GM_BF16) {
-    if (ng == 6 && um <= 2) GM_QKV_LAUNCH(bf16_raw, 6, 2);
-    if (ng == 6 && um <= 4) GM_QKV_LAUNCH(bf16_raw, 6, 4);
-    if (ng == 12 && um <= 2) GM_QKV_LAUNCH(bf16_raw, 12, 2);
+    if (ng == 6 && um == 2) GM_QKV_LAUNCH(bf16_raw, 6, 2);
+    if (ng == 6 && um == 4) GM_QKV_LAUNCH(bf16_raw, 6, 4);
+    if (ng == 12 && um == 2) GM_QKV_LAUNCH(bf16_raw, 12, 2);
   } else {
-    if (ng == 6 && um <= 2) GM_QKV_LAUNCH(float, 6, 2);
-    if (ng == 6 && um <= 4) GM_QKV_LAUNCH(float, 6, 4);
-    if (ng == 12 && um <= 2) GM_QKV_LAUNCH(float, 12, 2);
+    if (ng == 6 && um == 2) GM_QKV_LAUNCH(float, 6, 2);
+    if (ng == 6 && um == 4) GM_QKV_LAUNCH(float, 6, 4);
+    if (ng == 12 && um == 2) GM_QKV_LAUNCH(float, 12, 2);
   }
 #undef GM_QKV_LAUNCH
   return 0;
@@ -1353,11 +1377,12 @@ __global__ __launch_bounds__(64) void sample_index_kernel(const float* __restric
   if (ballot) {
     const int owner = __ffsll((long long)ballot) - 1;
     if (lane == owner) {
+      // (this running sum starts from excl = incl - loc, a rounded difference: it can end an ulp below incl, and then below a target the
+      //  ballot accepted -- the draw is the lane's last entry of positive probability, never a zero-probability one behind it)
       float c = excl;
-      idx = j1 - 1;
       for (int j = j0; j < j1; ++j) {
         c += pr[j];
-        if (c >= target && pr[j] > 0.f) { idx = j; break; }
+        if (pr[j] > 0.f) { idx = j; if (c >= target) break; }
       }
       out[row] = idx;
     }

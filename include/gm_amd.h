@@ -365,6 +365,31 @@ typedef struct GmDecodeDesc {
 } GmDecodeDesc;
 long long gm_decode_scratch_bytes(int B, int C, int M, int dtype);
 int gm_transformer_decode_step(const GmDecodeDesc* d, void* stream);
+/* The routes gm_transformer_decode_step takes for `d`, launching nothing (the step consults the same function): flags[GM_DECODE_PLAN_COUNT].
+ * They depend on dtype, geometry, null-ness of pointers and on whether pos_dev is given, never on the position.  Per-block entries are those
+ * of the last block (block 0 has no MLP partials in front of it and always reads the plain row). */
+#define GM_DECODE_PLAN_SPLIT_KV 0         /* 1: the window (max_len > 256) runs the attention over 16 key ranges */
+#define GM_DECODE_PLAN_QKV_NG 1           /* fused LayerNorm + q|k|v + attention ranges kernel: its NG (6 or 12), 0 = not fused */
+#define GM_DECODE_PLAN_QKV_UM 2           /* ... and its UM (2 or 4), 0 = not fused */
+#define GM_DECODE_PLAN_QKV_INPUT 3        /* GM_DECODE_INPUT_* */
+#define GM_DECODE_PLAN_OUT_MERGE 4        /* GM_DECODE_MERGE_* */
+#define GM_DECODE_PLAN_ATTN_ENTRY 5       /* GM_DECODE_ENTRY_* */
+#define GM_DECODE_PLAN_MLP_FUSED 6        /* 1: the MLP is one launch leaving K-slice partials */
+#define GM_DECODE_PLAN_KSPLIT_QKV 7       /* 1: the K-split small-row GEMM runs the q|k|v projection (0 also where the fused kernel replaces it) */
+#define GM_DECODE_PLAN_KSPLIT_OUT 8       /* ... the out-projection */
+#define GM_DECODE_PLAN_KSPLIT_MLP_UP 9    /* ... the MLP's C -> M projection (0 also where the fused MLP replaces it) */
+#define GM_DECODE_PLAN_KSPLIT_MLP_DOWN 10 /* ... the MLP's M -> C projection */
+#define GM_DECODE_PLAN_KSPLIT_LOGITS 11   /* ... to_logits */
+#define GM_DECODE_PLAN_COUNT 12
+#define GM_DECODE_INPUT_ROW 0             /* the q|k|v launch reads the residual-stream row */
+#define GM_DECODE_INPUT_MLP_MERGE 1       /* ... assembles it from the previous block's MLP partials */
+#define GM_DECODE_MERGE_NONE 0            /* not split */
+#define GM_DECODE_MERGE_OUT_PROJ 1        /* the out-projection's prologue merges the key-range partials */
+#define GM_DECODE_MERGE_COMBINE 2         /* a combine launch merges them */
+#define GM_DECODE_ENTRY_NONE 0            /* split */
+#define GM_DECODE_ENTRY_HOST_POS 1        /* single-launch attention through gm_attention_forward */
+#define GM_DECODE_ENTRY_DEVICE_POS 2      /* single-launch attention reading the key count on the device */
+int gm_transformer_decode_plan(const GmDecodeDesc* d, int* flags);
 /* after a draw: seq[b][*pos + 1] = idx[b]; tokens[b] = idx[b]; *pos += 1 (inferer.py:1237-1239 kept on the device) */
 int gm_decode_advance(int* pos, long long* tokens, const long long* idx, long long* seq, int B, long long seq_ld, void* stream);
 
