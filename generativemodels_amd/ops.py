@@ -1522,7 +1522,7 @@ def conv_wgrad(x: torch.Tensor, gy: torch.Tensor, kernel, stride=1, padding=0, o
                accumulate: bool = False) -> torch.Tensor:
     """Weight gradient of y = conv(x, W) (torch.nn.grad.conv*_weight): x, gy arena tensors (N, *spatial, C); returns fp32
     [Cout, Cin, *kernel].  kernel 1 or 3 (the same on every spatial axis), stride 1 or 2, `padding` = low-side pad (the high side
-    is implied by gy's extents)."""
+    is implied by gy's extents).  An empty batch or volume gives zeros (`out` is cleared, or left as it is under `accumulate`)."""
     require_device(x, gy, out)
     nsp = x.dim() - 2
     if nsp < 1 or nsp > 3 or gy.dim() != x.dim() or gy.dtype != x.dtype or gy.shape[0] != x.shape[0]:
@@ -1537,6 +1537,19 @@ def conv_wgrad(x: torch.Tensor, gy: torch.Tensor, kernel, stride=1, padding=0, o
     k, s_, p_ = tup(kernel), tup(stride), tup(padding)
     if len(set(k)) != 1 or len(set(s_)) != 1:
         raise ValueError("conv_wgrad: kernel and stride must be the same on every axis")
+    if x.numel() == 0 or gy.numel() == 0:
+        # an empty batch (or volume): the sum over no voxels.  Decided here, without a launch -- an empty tensor has no pointer to hand to the library
+        shape = (gy.shape[-1], x.shape[-1], *k)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs an existing gradient tensor")
+            return torch.zeros(shape, dtype=torch.float32, device=x.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32:
+            raise ValueError("conv_wgrad: out must be a contiguous fp32 [Cout, Cin, *kernel] tensor")
+        if not accumulate:
+            with torch.no_grad():
+                out.zero_()
+        return out
     if k[0] == 4 and s_[0] == 2 and nsp in (2, 3) and all(0 <= v <= 2 for v in p_):
         return _conv_wgrad_k4s2(x, gy, p_, out, accumulate)
     vec = 16 // x.element_size()

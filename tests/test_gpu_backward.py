@@ -63,7 +63,8 @@ WGRAD_CASES = {
 @pytest.mark.parametrize("case", list(WGRAD_CASES), ids=list(WGRAD_CASES))
 def test_conv_weight_gradient(case, dtype):
     """gm_conv_wgrad vs torch autograd (fp64) for every tile variant: 3-D / 2-D / stride 2 / 1x1-flat, ragged extents, partial
-    channel blocks, asymmetric padding."""
+    channel blocks, asymmetric padding.  (Every case here gives each work-group ONE tile; the split regimes -- walking work-groups, the 256-split
+    cap, one split -- are test_gpu_wgrad_matrix.py's.)"""
     ops = _ops()
     sp, n, cin, cout, k, s, plo, phi = WGRAD_CASES[case]
     nsp = len(sp)
