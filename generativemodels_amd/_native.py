@@ -186,6 +186,10 @@ PROTOTYPES = {
     "gm_avgpool2_pair": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_mmd_workspace_bytes": (c_ll, [c_ll, c_ll]),
     "gm_mmd": (C.c_int, [c_vp, c_vp, C.c_int, c_ll, c_ll, c_vp, c_vp, c_ll, c_vp]),
+    "gm_spade_block_apply": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_ll] + [C.c_int] * 10
+                             + [C.c_float, C.c_int, c_vp]),
+    "gm_leaky_relu": (C.c_int, [c_vp, c_vp, c_vp, C.c_float, c_ll, C.c_int, c_vp]),
+    "gm_kld": (C.c_int, [c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp]),
 }
 
 _lib = None

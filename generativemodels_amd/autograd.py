@@ -25,7 +25,7 @@ import torch
 
 from . import ops
 
-__all__ = ["cast", "scale", "spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "embedding", "silu", "upsample_conv", "attention", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["cast", "scale", "leaky_relu", "kld", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "embedding", "silu", "upsample_conv", "attention", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -731,6 +731,83 @@ class _SpadeModulate(torch.autograd.Function):
 
 def spade_modulate(xn: torch.Tensor, g: torch.Tensor, bm: torch.Tensor, act: str = "none") -> torch.Tensor:
     return _SpadeModulate.apply(xn, g, bm, act)
+
+
+class _LeakyReLU(torch.autograd.Function):
+    """LeakyReLU with a runtime slope (spade_network.py:82: 0.2); the backward is evaluated from the pre-activation (gm_leaky_relu)."""
+
+    @staticmethod
+    def forward(ctx, x, slope):
+        ctx.save_for_backward(x)
+        ctx.slope = slope
+        return ops.leaky_relu(x, slope)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        return ops.leaky_relu(x, ctx.slope, gy.contiguous()), None
+
+
+def leaky_relu(x: torch.Tensor, slope: float) -> torch.Tensor:
+    """x > 0 ? x : slope * x over any dense tensor; differentiable in x."""
+    return _LeakyReLU.apply(x, float(slope))
+
+
+class _NormModulateAct(torch.autograd.Function):
+    """y = LeakyReLU_slope(InstanceNorm / GroupNorm(x) * g + bm) (g, bm None: the plain norm + activation; slope None: no activation) as the ONE pass the
+    inference path runs (gm_spade_block_apply: the normalised tensor stays in fp32 registers, y is rounded once), so the training forward computes what
+    eval() computes.  Backward from y (y > 0 <=> pre-activation > 0 for slope >= 0), every step a native kernel: LeakyReLU' -> gm_spade_bwd over the
+    re-made normalised tensor -> the norm's backward."""
+
+    @staticmethod
+    def forward(ctx, x, g, bm, groups, eps, slope):
+        if slope is not None and slope < 0:
+            raise NotImplementedError("norm_modulate_act differentiates the activation from its output: slope >= 0")
+        scale, shift = ops.gn_scale_shift_composed(x, groups, eps, None, None)
+        y = ops.spade_block_apply(x, scale, shift, None if g is None else (g, bm), None, "none" if slope is None else "leakyrelu", slope or 0.0)
+        ctx.save_for_backward(x, g, bm, y, scale, shift, ops.channel_stats(x))
+        ctx.cfg = (groups, eps, slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, g, bm, y, scale, shift, stats = ctx.saved_tensors
+        groups, eps, slope = ctx.cfg
+        gu = gy.contiguous() if slope is None else ops.leaky_relu(y, slope, gy.contiguous())
+        dg = dbm = None
+        if g is not None:
+            gu, dg, dbm = ops.spade_backward(ops.gn_apply(x, scale, shift, "none"), g, bm, gu, "none")
+        try:
+            x._gm_cstats = stats  # the forward statistics: gn_backward does not re-read x for them
+        except Exception:  # pragma: no cover
+            pass
+        dx, _, _ = ops.gn_backward(x, gu, scale, shift, None, groups, eps, "none", want_affine_grads=False)
+        return dx, dg, dbm, None, None, None
+
+
+def norm_modulate_act(x: torch.Tensor, g: Optional[torch.Tensor], bm: Optional[torch.Tensor], groups: int, eps: float,
+                      slope: Optional[float]) -> torch.Tensor:
+    """LeakyReLU_slope(norm(x) * g + bm) over an arena tensor, the norm parameter-free with `groups` groups; differentiable in x, g and bm."""
+    return _NormModulateAct.apply(x, g, bm, groups, eps, None if slope is None else float(slope))
+
+
+class _KLD(torch.autograd.Function):
+    """KLDLoss (spade_network.py:27-34) as one fp32 scalar; the backward re-reads (mu, logvar) and scales by the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar):
+        ctx.save_for_backward(mu, logvar)
+        return ops.kld(mu, logvar)
+
+    @staticmethod
+    def backward(ctx, g):
+        mu, logvar = ctx.saved_tensors
+        return ops.kld(mu, logvar, upstream=g.to(torch.float32).contiguous(), want_value=False, want_grads=True)
+
+
+def kld(mu: torch.Tensor, logvar: torch.Tensor) -> torch.Tensor:
+    """-0.5 * sum(1 + logvar - mu^2 - exp(logvar)) (fp32 scalar); differentiable in mu and logvar."""
+    return _KLD.apply(mu, logvar)
 
 
 class _Scale(torch.autograd.Function):

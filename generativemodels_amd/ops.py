@@ -583,6 +583,89 @@ def spade_apply(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, g: to
     return out
 
 
+BLOCK_ACT = {"none": 0, "silu": 1, "leakyrelu": 3}  # activation codes of gm_spade_block_apply (LeakyReLU takes its slope as an argument; ReLU is slope 0)
+
+
+def spade_block_apply(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, maps0: Optional[tuple] = None, maps1: Optional[tuple] = None,
+                      act: str = "none", slope: float = 0.2, up: bool = False, out0: Optional[torch.Tensor] = None,
+                      out1: Optional[torch.Tensor] = None):
+    """One pass over a SPADEResNetBlock's input (reference: spade_network.py:118-130): t = x * scale[n, c] + shift[n, c], then
+    y0 = act(t * g0 + b0) (maps0 = (g0, b0); None: y0 = act(t), a plain norm + activation) and, with maps1 = (g1, b1), y1 = t * g1 + b1 (the
+    shortcut's norm_s: no activation).  up: x lives on the half-resolution grid and every output voxel reads its nearest-2x source voxel --
+    (scale, shift) are then the statistics of x itself, which the up-sampling leaves unchanged.  act: "none", "silu" or "leakyrelu" (slope).
+    Maps and outputs may be channel slices of wider arena buffers.  -> y0, or (y0, y1) with maps1."""
+    require_device(x, scale, shift, out0, out1, *(maps0 or ()), *(maps1 or ()))
+    n, c = x.shape[0], x.shape[-1]
+    nsp = x.dim() - 2
+    if nsp not in (2, 3):
+        raise ValueError("spade_block_apply needs 2-D or 3-D data")
+    src = (1,) * (3 - nsp) + tuple(x.shape[1:-1])
+    osp = tuple(s * 2 for s in x.shape[1:-1]) if up else tuple(x.shape[1:-1])
+    dst = (1,) * (3 - nsp) + osp
+    oshape = (n, *osp, c)
+    if scale.shape != (n, c) or shift.shape != (n, c) or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.stride(0) != shift.stride(0):
+        raise ValueError("spade_block_apply: scale/shift must be matching [N, C] (slices of) fp32 tables")
+    for maps in (maps0, maps1):
+        if maps is not None and (len(maps) != 2 or any(m.shape != oshape or m.dtype != x.dtype for m in maps) or arena_ld(maps[0]) != arena_ld(maps[1])):
+            raise ValueError("spade_block_apply: a map pair must match the output grid (shape, dtype) and share a row pitch")
+    if maps1 is None and out1 is not None:
+        raise ValueError("spade_block_apply: a second output needs a second map pair")
+    outs = []
+    for o, wanted in ((out0, True), (out1, maps1 is not None)):
+        if wanted and o is None:
+            o = torch.empty(oshape, dtype=x.dtype, device=x.device)
+        elif wanted and (o.shape != oshape or o.dtype != x.dtype):
+            raise ValueError("spade_block_apply: an output must match the output grid (shape, dtype)")
+        outs.append(o)
+    y0, y1 = outs
+    ss_ld = scale.stride(0) if n > 1 else max(scale.stride(0), c)
+    streams = 2 + (2 if maps0 is not None else 0) + (3 if maps1 is not None else 0)  # (x is counted at the output resolution: an upper bound with up)
+    g0, b0 = maps0 if maps0 is not None else (None, None)
+    g1, b1 = maps1 if maps1 is not None else (None, None)
+    _timed(f"spade_block_apply<{str(x.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float(streams * x.element_size() * math.prod(oshape)), shape=str(oshape)),
+           lambda: check(lib().gm_spade_block_apply(x.data_ptr(), arena_ld(x), scale.data_ptr(), shift.data_ptr(), ss_ld, _ptr(g0), _ptr(b0),
+                                                    0 if g0 is None else arena_ld(g0), y0.data_ptr(), arena_ld(y0), _ptr(g1), _ptr(b1),
+                                                    0 if g1 is None else arena_ld(g1), _ptr(y1), 0 if y1 is None else arena_ld(y1), n, *src, *dst, c,
+                                                    int(bool(up)), BLOCK_ACT[act], float(slope), dt_code(x.dtype), _stream()), "gm_spade_block_apply"))
+    return y0 if maps1 is None else (y0, y1)
+
+
+def leaky_relu(x: torch.Tensor, slope: float, gy: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LeakyReLU with a runtime slope: x > 0 ? x : slope * x (gy None), or gy * (x > 0 ? 1 : slope) from the pre-activation x.  Any dense layout."""
+    require_device(x, gy)
+    x = x.contiguous()
+    if gy is not None:
+        if gy.shape != x.shape or gy.dtype != x.dtype:
+            raise ValueError("leaky_relu: gy must match x")
+        gy = gy.contiguous()
+    out = torch.empty_like(x)
+    _timed(f"leaky_relu<{str(x.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float((2 if gy is None else 3) * x.element_size() * x.numel()), shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_leaky_relu(x.data_ptr(), _ptr(gy), out.data_ptr(), float(slope), x.numel(), dt_code(x.dtype), _stream()), "gm_leaky_relu"))
+    return out
+
+
+def kld(mu: torch.Tensor, logvar: torch.Tensor, upstream: Optional[torch.Tensor] = None, want_value: bool = True, want_grads: bool = False):
+    """-0.5 * sum(1 + logvar - mu^2 - exp(logvar)) as an fp32 scalar tensor (one work-group, fp64, fixed order: bitwise repeatable), and / or its
+    gradients (dmu, dlogvar) = upstream * (mu, -0.5 * (1 - exp(logvar))) in the dtype of mu; upstream: an fp32 scalar tensor (None: 1).
+    -> value, (dmu, dlogvar), or (value, dmu, dlogvar)."""
+    require_device(mu, logvar, upstream)
+    if mu.shape != logvar.shape or mu.dtype != logvar.dtype:
+        raise ValueError("kld: mu and logvar must match in shape and dtype")
+    if not (want_value or want_grads):
+        raise ValueError("kld: nothing asked for")
+    if upstream is not None and (upstream.numel() != 1 or upstream.dtype != torch.float32):
+        raise ValueError("kld: the upstream gradient is one fp32 value")
+    mu, logvar = mu.contiguous(), logvar.contiguous()
+    value = torch.empty((), dtype=torch.float32, device=mu.device) if want_value else None
+    dmu, dlv = (torch.empty_like(mu), torch.empty_like(logvar)) if want_grads else (None, None)
+    _timed(f"kld<{str(mu.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float(2 * mu.element_size() * mu.numel()), shape=str(tuple(mu.shape))),
+           lambda: check(lib().gm_kld(mu.data_ptr(), logvar.data_ptr(), mu.numel(), _ptr(value), _ptr(upstream), _ptr(dmu), _ptr(dlv), dt_code(mu.dtype),
+                                      _stream()), "gm_kld"))
+    if not want_grads:
+        return value
+    return (dmu, dlv) if not want_value else (value, dmu, dlv)
+
+
 class VirtualCat:
     """Channel concatenation that is never materialised (reference: torch.cat([h, skip], dim=1), diffusion_model_unet.py:1232,
     1340,1461): its consumers read the parts directly."""

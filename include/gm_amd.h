@@ -527,6 +527,21 @@ long long gm_mmd_workspace_bytes(long long B, long long F);
 int gm_mmd(const void* y, const void* y_pred, int dtype, long long B, long long F, float* out, void* workspace, long long workspace_bytes,
            void* stream);
 
+/* ---- SPADE VAE-GAN generator (networks/nets/spade_network.py) -----------------------------------------------------------
+ * One pass of a SPADEResNetBlock's norms over the OUTPUT grid (Do, Ho, Wo; a 2-D grid has Do = Ds = 1):
+ *   t = x[n][src(v)][c] * scale[n][c] + shift[n][c],   y0 = act0(t * g0 + b0)  (g0 = b0 = NULL: y0 = act0(t)),   y1 = t * g1 + b1  (only when g1 != NULL)
+ * src(v) = v when up = 0 (the grids are equal); with up = 1 x lives on the half-resolution grid (Ds, Hs, Ws) and src(d, h, w) = (d >> 1, h >> 1, w >> 1):
+ * the nearest 2x up-sampling is never written, and (scale, shift) are the instance-norm statistics of x itself (replication changes neither the mean nor the
+ * biased variance).  act0: 0 none, 1 SiLU, 3 LeakyReLU(slope).  Every operand has its own row pitch in elements; the maps and outputs are in the dtype of x. */
+int gm_spade_block_apply(const void* x, long long x_ld, const float* scale, const float* shift, long long ss_ld, const void* g0, const void* b0,
+                         long long gb0_ld, void* y0, long long y0_ld, const void* g1, const void* b1, long long gb1_ld, void* y1, long long y1_ld,
+                         int N, int Ds, int Hs, int Ws, int Do, int Ho, int Wo, int C, int up, int act0, float slope, int dtype, void* stream);
+/* LeakyReLU with a runtime slope over a contiguous tensor: gy = NULL out = x > 0 ? x : slope * x, otherwise out = gy * (x > 0 ? 1 : slope) from the pre-activation x */
+int gm_leaky_relu(const void* x, const void* gy, void* out, float slope, long long total, int dtype, void* stream);
+/* KLDLoss: out[0] (fp32, may be NULL) = -0.5 * sum(1 + logvar - mu^2 - exp(logvar)) over `total` elements: one work-group, fp64, fixed order.  dmu, dlogvar (both or
+ * neither, dtype of mu) = up * mu and up * -0.5 * (1 - exp(logvar)), `up` = upstream[0] read on the device (NULL: 1). */
+int gm_kld(const void* mu, const void* logvar, long long total, float* out, const float* upstream, void* dmu, void* dlogvar, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
