@@ -83,12 +83,17 @@ class GmWgradDesc(C.Structure):
                 ("stride", C.c_int), ("pd", C.c_int), ("ph", C.c_int), ("pw", C.c_int), ("dtype", C.c_int), ("accumulate", C.c_int)]
 
 
+class GmResizeDesc(C.Structure):
+    _fields_ = [("n_in", C.c_int * 3), ("n_out", C.c_int * 3), ("start", c_vp * 3), ("index", c_vp * 3), ("weight", c_vp * 3)]
+
+
 # name -> (restype, argtypes); mirrors include/gm_amd.h one to one (tests/test_abi.py checks the export list)
 PROTOTYPES = {
     "gm_abi_version": (C.c_int, []),
     "gm_last_error": (C.c_char_p, []),
     "gm_sched_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_ll, C.c_int, C.POINTER(GmStepParams), c_vp]),
     "gm_nearest_resize": (C.c_int, [c_vp, c_ll, c_vp, c_ll] + [C.c_int] * 9 + [c_vp]),
+    "gm_resize_taps": (C.c_int, [c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_int, C.POINTER(GmResizeDesc), C.c_int, c_vp]),
     "gm_axpby_rows": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, C.c_int, c_vp]),
     "gm_likelihood_term": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_ll, C.c_int, C.POINTER(GmKlParams), c_vp]),
     "gm_lincomb": (C.c_int, [C.POINTER(c_vp), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, c_vp, c_ll, C.c_int, c_vp]),

@@ -14,6 +14,7 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
                   bf16 LDS-DMA flash backward, the bf16-MFMA score pass + weight-gradient kernels, the fused fp32 flash backward (head dims
                   zero-padded to 16 .. 256 for these two), or per (sample, head) in fp32 on the GEMM / weight-gradient kernels (the only one
                   for head dims above 256, unpadded, up to 8192 tokens)
+  resize          forward: F.interpolate (every mode) as one launch of the separable tap kernel; backward: the same kernel on the transposed tables
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -25,7 +26,7 @@ import torch
 
 from . import ops
 
-__all__ = ["cast", "scale", "leaky_relu", "kld", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "embedding", "silu", "upsample_conv", "attention", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["cast", "scale", "leaky_relu", "kld", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -688,6 +689,25 @@ class _Resample2x(torch.autograd.Function):
 
 def resample2x(x: torch.Tensor, mode: str) -> torch.Tensor:
     return _Resample2x.apply(x, mode)
+
+
+class _Resize(torch.autograd.Function):
+    """F.interpolate of an arena tensor on the separable tap kernel (SpatialRescaler's stages, networks/blocks/encoder_modules.py:77-78); the
+    gradient is the same kernel over the plan's transposed tables."""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan = plan
+        return ops.resize(x, plan.mode, plan=plan)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return ops.resize_backward(gy.contiguous(), ctx.plan), None
+
+
+def resize(x: torch.Tensor, mode: str, size=None, scale_factor=None) -> torch.Tensor:
+    """F.interpolate(x, size=size, scale_factor=scale_factor, mode=mode) (align_corners=False) of an arena tensor; differentiable in x."""
+    return _Resize.apply(x, ops.resize_plan(x, mode, size, scale_factor))
 
 
 class _Embedding(torch.autograd.Function):

@@ -17,7 +17,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native as nat
-from ._native import GmAttnBwdDesc, GmAttnDesc, GmConvDesc, GmGnTables, GmKlParams, GmStepParams, GmWgradDesc, check, lib
+from ._native import GmAttnBwdDesc, GmAttnDesc, GmConvDesc, GmGnTables, GmKlParams, GmResizeDesc, GmStepParams, GmWgradDesc, check, lib
+from .resize_plan import ResizePlan, plan_for
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 ACT = {"none": 0, "silu": 1, "relu": 2}
@@ -514,6 +515,55 @@ def nearest_resize(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     check(lib().gm_nearest_resize(x.data_ptr(), arena_ld(x), out.data_ptr(), arena_ld(out), x.shape[0], *si, *so, x.shape[-1],
                                   dt_code(x.dtype), _stream()), "gm_nearest_resize")
     return out
+
+
+def _resize_launch(src: torch.Tensor, plan: ResizePlan, transposed: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gm_resize_taps over `plan`'s tables (forward) or their transposes (the gradient: src = the upstream gradient, extents exchanged)."""
+    require_device(src, out)
+    sp_in, sp_out = (plan.out_spatial, plan.in_spatial) if transposed else (plan.in_spatial, plan.out_spatial)
+    if tuple(src.shape[1:-1]) != tuple(sp_in):
+        raise ValueError(f"resize: tensor with spatial extents {tuple(src.shape[1:-1])} against a plan for {tuple(sp_in)}")
+    n, c = src.shape[0], src.shape[-1]
+    ld = arena_ld(src)
+    if out is None:
+        out = torch.empty((n, *sp_out, c), dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != (n, *sp_out, c) or out.dtype != src.dtype or out.device != src.device:
+        raise ValueError(f"resize: out must be a {(n, *sp_out, c)} {src.dtype} arena tensor on {src.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    if out.numel() == 0:  # an empty batch or no channels: nothing to launch (an empty tensor has no pointer to hand to the library)
+        return out
+    desc = plan.launch_cache.get((src.device, transposed))
+    if desc is None:  # the descriptor of one direction on one device: extents and table pointers, fixed for the life of the plan
+        tabs = plan.device_tables(src.device, transposed)
+        pad = (1,) * (3 - len(sp_in))
+        desc = plan.launch_cache[(src.device, transposed)] = GmResizeDesc((C.c_int * 3)(*pad, *sp_in), (C.c_int * 3)(*pad, *sp_out), (C.c_void_p * 3)(*tabs.start),
+                                                                          (C.c_void_p * 3)(*tabs.index), (C.c_void_p * 3)(*tabs.weight))
+    taps = plan.max_taps_transposed if transposed else plan.max_taps
+    meta = dict(flops=2.0 * taps * out.numel(), bytes=float((src.numel() + out.numel()) * src.element_size() + plan.table_bytes(transposed)),
+                shape=f"{plan.mode} {tuple(src.shape)}->{tuple(out.shape)}" + (" (gradient)" if transposed else ""))
+    _timed("resize_taps", meta, lambda: check(lib().gm_resize_taps(src.data_ptr(), ld, out.data_ptr(), arena_ld(out), n, c, C.byref(desc), dt_code(src.dtype),
+                                                                   _stream()), "gm_resize_taps"))
+    return out
+
+
+def resize_plan(x: torch.Tensor, mode: str, size=None, scale_factor=None) -> ResizePlan:
+    """The cached plan (resize_plan.py) of F.interpolate(x, size=size, scale_factor=scale_factor, mode=mode) for an arena tensor (N, *spatial, C)."""
+    return plan_for(mode, tuple(x.shape[1:-1]), size, scale_factor)
+
+
+def resize(x: torch.Tensor, mode: str, size=None, scale_factor=None, plan: Optional[ResizePlan] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.interpolate(mode = nearest | linear | bilinear | trilinear | bicubic | area, align_corners=False, antialias=False) of an arena tensor
+    (N, *spatial, C), which may be a channel slice of a wider buffer: one launch of the separable tap kernel for every mode and geometry (an identity
+    geometry included -- no special case that could drift from torch).  `plan`: the plan of this geometry when the caller holds it already
+    (resize_plan(x, ...), which resize_backward takes too); `out`: write into this arena tensor (a channel slice of a wider buffer) instead of a new one."""
+    if plan is None:
+        plan = resize_plan(x, mode, size, scale_factor)
+    return _resize_launch(x, plan, False, out)
+
+
+def resize_backward(gy: torch.Tensor, plan: ResizePlan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of resize with respect to its input: the same kernel over the plan's transposed tables (per input voxel the outputs that read it, in
+    ascending order -- no atomics, bitwise reproducible)."""
+    return _resize_launch(gy, plan, True, out)
 
 
 def gn_scale_shift(x: torch.Tensor, groups: int, eps: float, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor],
