@@ -48,14 +48,36 @@ struct GmConvDesc {
   // writing its fp32 partial accumulators to kpartial[ks][n * V + voxel][Cout]; gm_conv_forward then runs the combine kernel (sum of the
   // slices + bias / timestep row / residual / activation / output statistics).  ksplit <= 1: off.
   int ksplit; float* kpartial;
-  // optional GroupNorm prologue given as STATISTICS instead of (pre_scale, pre_shift) -- tile configurations 24 / 25 (conv_sn.hip) only: the consumer folds the
-  // per-tile partials of its input (up to two channel-concatenated sources, S_i <= 64 rows of [N][C_i][2] fp64 each, as gm_gn_finalize_channels takes them) and
+  // optional GroupNorm prologue given as STATISTICS instead of (pre_scale, pre_shift) -- tile configurations 24 / 25 (conv_sn.hip) and the K slices of a split
+  // cfg 11 launch (conv_sk.hip): the consumer folds the per-tile partials of its input (up to two channel-concatenated sources, S_i <= GN_SHORT_MAX_ROWS = 128
+  // rows of [N][C_i][2] fp64 each, as gm_gn_finalize_channels takes them) and
   // forms scale = rstd * gamma, shift = beta - mean * rstd * gamma itself, in its prologue: bit-identical to gm_gn_finalize_channels, one launch less per norm.
   // pre_stats[0] == NULL: off (pre_scale / pre_shift as before).  pre_act applies as usual.
   const double* pre_stats[2]; int pre_S[2]; int pre_C[2];
   const float* pre_gamma; const float* pre_beta;   // [Cin] fp32 or NULL (1 / 0)
   float pre_eps; int pre_groups;
 };
+
+// ---- host predicates shared by the eligibility tests of the LDS-DMA kernels ---------------------------------------------------------------------------------
+static inline bool gm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the statistics form of a GroupNorm prologue (GmConvDesc.pre_stats / GmGnTables): one or two 16-byte aligned sources of 1 .. GN_SHORT_MAX_ROWS rows whose
+// channels add up to cin; no second source, no second channel count.  (Each consumer adds the bounds of its own LDS tables.)
+static inline bool gm_gn_stats_form_ok(const double* const stats[2], const int S[2], const int C[2], int cin) {
+  return stats[0] != nullptr && S[0] >= 1 && S[0] <= GN_SHORT_MAX_ROWS && C[0] > 0 &&
+         ((stats[1] == nullptr && C[1] == 0 && C[0] == cin) || (stats[1] != nullptr && S[1] >= 1 && S[1] <= GN_SHORT_MAX_ROWS && C[1] > 0 && C[0] + C[1] == cin)) &&
+         gm_aligned16(stats[0]) && gm_aligned16(stats[1]);
+}
+// the second input source of a virtual channel concatenation: same geometry, chunk-aligned split inside C_in, vector-aligned pitch and base
+static inline bool gm_conv_second_source_ok(const GmConvDesc* d, int bk, int vecw) {
+  return d->x2 == nullptr || (d->cin_split > 0 && d->cin_split < d->Cin && d->cin_split % bk == 0 && d->x2_ld % vecw == 0 && gm_aligned16(d->x2));
+}
+// the fused 1x1 shortcut: packed weights and one or two sources of whole K chunks with vector-aligned pitch and base
+static inline bool gm_conv_shortcut_ok(const GmConvDesc* d, int bk, int vecw) {
+  if (!d->skip_x[0]) return true;
+  for (int i = 0; i < 2; ++i)
+    if (d->skip_x[i] && !(d->skip_cin[i] > 0 && d->skip_cin[i] % bk == 0 && d->skip_ld[i] % vecw == 0 && gm_aligned16(d->skip_x[i]))) return false;
+  return d->skip_w != nullptr;
+}
 
 // slot count of the zero-initialised, atomically accumulated statistic tables the BACKWARD kernels still use ([GM_STAT_SLOTS][N][C][2];
 // gm_gn_bwd_stats, gm_layernorm_bwd).  The forward tables (convolution epilogues, gm_gn_channel_stats) hold one partial per tile instead.

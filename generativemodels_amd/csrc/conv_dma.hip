@@ -93,13 +93,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void conv_dma_kernel(const GmConvDes
   static_assert(!WGEN || (S == 1 && (WROWS / 16) % NW == 0), "general panel distribution: whole pieces per wave");
   static_assert(WROWS == (KS == 3 ? 3 : 2) * BN, "G taps per weight panel");
   static_assert(NGROUPS % RING == 0, "the ring slot of a group is a compile-time constant");
-#ifdef GM_CONV_LDS_EPILOGUE
-  constexpr bool DIRECT_W = false;
-#else
   // weight rows in direct_chan() order (the register-direct epilogue below).  Not for the sub-pixel form: its output voxels are every other
   // voxel of a row, a store instruction would write sixteen isolated 64-byte halves of 128-byte lines (measured: cfg 17 0.84 -> 1.04 ms)
   constexpr bool DIRECT_W = NFR == 4 && KS == 3;
-#endif
 
   extern __shared__ __attribute__((aligned(1024))) char smem[];  // [patch 42 KiB][3 weight panels x 12 KiB][addend vector 512 B]
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
@@ -333,13 +329,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void conv_dma_kernel(const GmConvDes
   static_assert(PVT_OFF == PATCH_BYTES + RING_BYTES + 512, "the placement table follows the addend vector");
   float* addv = reinterpret_cast<float*>(smem + PATCH_BYTES + RING_BYTES);  // per-channel epilogue addend of this work-group's BN output channels
   // DIRECT: the register-direct epilogue (conv_dma_shared.h): the weight rows of a panel are DMA'd in direct_chan() order, so that a lane's
-  // accumulators are 16-byte runs of the output row and no LDS transpose is needed (64-channel tiles; bench A/B: -DGM_CONV_LDS_EPILOGUE restores
-  // the transposed form everywhere)
-#ifdef GM_CONV_LDS_EPILOGUE
-  constexpr bool DIRECT = false;
-#else
+  // accumulators are 16-byte runs of the output row and no LDS transpose is needed (64-channel tiles; the other tiles, and the rare output-activation
+  // form, keep the transposed one.  Round 5 A/B against the transposed form everywhere: profiles/r05_phase_skew_sweep.txt)
   constexpr bool DIRECT = NFR == 4 && KS == 3;
-#endif
   constexpr int EPASSES = (NFR * 16 * (int)sizeof(T) + 127) / 128;
   constexpr int CH_PER_PASS = 128 / (int)sizeof(T);
   static_assert(EPASSES <= 4, "at most 4 epilogue passes (128 output channels in fp32)");
@@ -459,76 +451,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void conv_dma_kernel(const GmConvDes
 #define mma_tap(set) mma_tap_pw(set, KS == 2 ? g / 4 : 0)  /* every tap multiplied inside iteration g belongs to group g */
         constexpr int NMMA = MF * 4 * (sizeof(T) == 2 ? 1 : 4), NRD = MF + 4;
         static_assert(G == 3 || G == 2, "taps per panel");
-#ifdef GM_CONV_EARLY_BARRIER
-        // Round 3: the group barrier one tap EARLIER.  The MFMA pipe holds no queue -- a wave's instruction stream advances in step with its
-        // MFMAs -- so whatever a wave waits for at the end-of-group barrier is exposed unless the partner work-group's wave has MFMAs to issue.
-        // The round-2 order (below) reached the barrier right after issuing the last tap's eight operand reads and had to retire them there
-        // (`lgkmcnt(0)`: ~100-150 cycles of LDS latency per group), because the panel request that followed the barrier overwrote the ring slot
-        // those reads came from one group later.  Here the barrier sits between the MFMAs of tap 0 and the reads of tap 2: the only reads in
-        // flight are tap 1's, issued a whole tap (256 MFMA cycles) earlier, the wait is free, and the panel request moves behind it:
-        //   read tap 1 | MFMA tap 0 | wait panel t+1 + barrier B_g | request panel t+2 -> slot (g-1) % RING | read tap 2 | MFMA tap 1 |
-        //   read tap 0 of group g+1 | MFMA tap 2
-        // B_g: every wave has retired its reads of group g-1 (program order + lgkmcnt(0)), so slot (g-1) % RING is free; panel t+1 (requested
-        // behind B_{g-1}, one full group ago) has landed for every wave (vmcnt(0): nothing newer is in flight) and is visible behind the barrier.
-#pragma unroll
-        for (int g = 0; g < NGROUPS; ++g) {
-          const int t = chunk * NGROUPS + g;
-          const int X = (g * G) & 1, Y = X ^ 1;
-          const int LASTSET = (g * G + G - 1) & 1, NEXTSET = ((g + 1) * G) & 1;
-          if (g == 0) read_tap(0, 0, X);
-          read_tap(g, 1, Y);
-          mma_tap(X);
-          if (g == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2 * NRD, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, NMMA, 0);
-          dma_wait<0>();
-          __builtin_amdgcn_s_barrier();
-#ifdef GM_CONV_DMA_INTERLEAVE
-          // the panel request's WPW LDS-DMA instructions (each ~8 issue slots with its address select and M0 hand-over) one at a time between the
-          // quarters of tap 1's MFMAs instead of in one lump of ~24 instructions during which the matrix pipe -- which holds no queue -- runs dry
-          const bool want_w = g < NGROUPS - 2 || !last_chunk;
-          if (G == 3) {
-            read_tap(g, 2, X);
-#pragma unroll
-            for (int nf = 0; nf < 4; ++nf) {
-#pragma unroll
-              for (int mf = 0; mf < MF; ++mf) Mma<T>::run(wf[Y][nf], xf[Y][mf], acc[nf][mf]);
-              if (want_w && nf < WPW) issue_w_pieces(t + 2, (g + 2) % RING, nf, nf + 1);
-            }
-            if (want_w && WPW > 4) issue_w_pieces(t + 2, (g + 2) % RING, 4, WPW);
-          } else if (want_w) {
-            issue_w(t + 2, (g + 2) % RING);
-          }
-#else
-          if (g < NGROUPS - 2 || !last_chunk) issue_w(t + 2, (g + 2) % RING);
-          if (G == 3) {
-            read_tap(g, 2, X);
-            mma_tap(Y);
-            __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, NMMA, 0);
-          }
-#endif
-          if (g == NGROUPS - 1) {
-            if (!last_chunk) {
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-              __builtin_amdgcn_s_barrier();  // every wave is done with this chunk's patch
-              issue_patch(chunk + 1);
-              if (pre) load_affine(chunk + 1);
-              dma_wait<0>();                 // patch + the panel in flight
-              if (pre) transform_patch();
-              __builtin_amdgcn_s_barrier();
-            }
-          } else {
-            read_tap(g + 1, 0, NEXTSET);     // panel t+1: landed and published by B_g
-          }
-          mma_tap(LASTSET);
-          if (g < NGROUPS - 1) {
-            __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, NMMA, 0);
-          }
-          if (chunk - c_begin < 5) TL_STAMP(3 + (chunk - c_begin) * 10 + g);
-        }
-#else
 #pragma unroll
         for (int g = 0; g < NGROUPS; ++g) {
           const int t = chunk * NGROUPS + g;
@@ -572,7 +494,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void conv_dma_kernel(const GmConvDes
           }
           if (chunk - c_begin < 5) TL_STAMP(3 + (chunk - c_begin) * 10 + g);  // after the barrier that ends group g (g = 8: incl. the chunk boundary)
         }
-#endif
       } else {
 #pragma unroll
       for (int g = 0; g < NGROUPS; ++g) {
@@ -1174,18 +1095,11 @@ extern "C" int gm_conv_dma_eligible(const GmConvDesc* d) {
              (reinterpret_cast<uintptr_t>(d->pre_shift) & 15) == 0 && (d->Cin % 4) == 0))) ||
           // ... or from the input's statistic tables (GmConvDesc.pre_stats): the K slices of a split launch only (conv_sk.hip finalises the norm in its prologue)
           (d->pre_stats[0] != nullptr && d->cfg == 11 && gm_conv_sk_eligible(d))) &&
-         // second input source (virtual channel concatenation): same geometry, chunk-aligned split
-         (d->x2 == nullptr || (d->cin_split > 0 && d->cin_split < d->Cin && d->cin_split % bk == 0 && d->x2_ld % vecw == 0 &&
-                               (reinterpret_cast<uintptr_t>(d->x2) & 15) == 0)) &&
+         gm_conv_second_source_ok(d, bk, vecw) && gm_conv_shortcut_ok(d, bk, vecw) &&
          d->ltd == (d->cfg == 16 || d->cfg == 18 || d->cfg == 19 ? 3 : (s == 1 ? 2 : 1)) && d->lth == 2 &&
          d->ltw == 4 && d->Cout % vecw == 0 && d->y_ld % vecw == 0 && (reinterpret_cast<uintptr_t>(d->y) & 15) == 0 &&
          (!d->res || (d->res_ld % vecw == 0 && (reinterpret_cast<uintptr_t>(d->res) & 15) == 0)) &&
-         (long long)d->N * d->Ds * d->Hs * d->Ws < (1LL << 31) && (long long)d->N * d->Do * d->Ho * d->Wo < (1LL << 31) &&
-         (!d->skip_x[0] ||
-          (d->skip_w && d->skip_cin[0] > 0 && d->skip_cin[0] % bk == 0 && d->skip_ld[0] % vecw == 0 &&
-           (reinterpret_cast<uintptr_t>(d->skip_x[0]) & 15) == 0 &&
-           (!d->skip_x[1] || (d->skip_cin[1] > 0 && d->skip_cin[1] % bk == 0 && d->skip_ld[1] % vecw == 0 &&
-                              (reinterpret_cast<uintptr_t>(d->skip_x[1]) & 15) == 0))));
+         (long long)d->N * d->Ds * d->Hs * d->Ws < (1LL << 31) && (long long)d->N * d->Do * d->Ho * d->Wo < (1LL << 31);
 }
 
 #endif

@@ -16,7 +16,7 @@
 // Same tile (4x4x16 voxels x 64 channels, 8 waves x 32 voxels), same LDS layouts, same packed weights and the same order of MFMAs per
 // accumulator as cfg 11: the partials are bit-identical to the round-3 path (tests/test_gpu_kernels.py pins that).
 // (reference op: the ResnetBlock / Upsample convolutions of the latent UNet, generative/networks/nets/diffusion_model_unet.py:589-696)
-#include "conv_dma_shared.h"
+#include "conv_patch.h"
 
 __device__ __attribute__((aligned(64))) unsigned int gm_sk_zero_row[16] = {0};  // the source of every padding row
 
@@ -36,10 +36,11 @@ __device__ __forceinline__ void dma16_base(const void* sbase, unsigned voff, uns
 namespace sk {
 constexpr int NW = 8, MF = 2, NFR = 4, KS = 3, G = 3, NGROUPS = 9;
 constexpr int TD = 4, TH = 4, TW = 16, BM = 256, BN = 64;
-constexpr int PD = 6, PH = 6, PW = 18, PLANE = 112, PROWS = PD * PLANE, PPIECES = PROWS / 16, PPW = (PPIECES + NW - 1) / NW;
+constexpr int PD = 6, PH = 6, PW = 18, PLANE = 112, PROWS = PD * PLANE;
+typedef PatchGeom<NW, PLANE, PW, PH, PROWS> PG;
 constexpr int WROWS = G * BN, WPW = 2;
 constexpr int PATCH_BYTES = PROWS * DMA_ROWB, WBUF_BYTES = WROWS * DMA_ROWB;
-constexpr int AFF_OFF = PATCH_BYTES + NGROUPS * WBUF_BYTES, AFF_WAVE = 256;
+constexpr int AFF_OFF = PATCH_BYTES + NGROUPS * WBUF_BYTES, AFF_WAVE = PATCH_AFF_WAVE;
 // PRE from the input's statistic tables (GmConvDesc.pre_stats: the GroupNorm finalised HERE, conv_sn.hip's recipe, round 6): behind the per-wave copies, the (scale |
 // shift) of THIS SLICE's channels (<= TAB_CH) and the fp64 channel sums of the groups they belong to (<= COVER_CH channels: the slice + the rest of its first and last group)
 constexpr int TAB_CH = 128, COVER_CH = 256;
@@ -57,7 +58,6 @@ template <typename T, bool PRE>
 __global__ __launch_bounds__(512, 2) void conv_sk_kernel(const GmConvDesc p) {
   using namespace sk;
   constexpr int BK = ConvTraits<T>::BK;
-  constexpr int VECW = ConvTraits<T>::VECW;
   extern __shared__ __attribute__((aligned(1024))) char smem[];  // [patch][9 weight panels][8 x (scale | shift) of the chunk]
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -72,17 +72,15 @@ __global__ __launch_bounds__(512, 2) void conv_sk_kernel(const GmConvDesc p) {
   }
 #define SK_STAMP(k) do { if (stamps) stamps[k] = __builtin_readcyclecounter(); } while (0)
 
-  // ---- the work item: (K slice, tile, channel block), dealt to the XCDs in contiguous ranges like conv_dma.hip's work list ----------------
+  // ---- the work item: (K slice, tile, channel block) -----------------------------------------------------------------------------------------
   const int ntd = (p.Do + TD - 1) / TD, nth = (p.Ho + TH - 1) / TH, ntw = (p.Wo + TW - 1) / TW;
   const int ncb = (p.Cout + BN - 1) / BN;
   const int ksplit = p.ksplit;
   const int nchunks = p.Cin / BK, cout_pad = (p.Cout + 15) & ~15;
   const int cps = (nchunks + ksplit - 1) / ksplit;
   const unsigned nwork = (unsigned)p.N * ntd * nth * ntw * ncb * (unsigned)ksplit;
-  const unsigned xcd = blockIdx.x & 7;
-  const unsigned q8 = nwork >> 3, r8 = nwork & 7, cx = q8 + (xcd < r8 ? 1u : 0u), sx = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  if ((blockIdx.x >> 3) >= cx) return;  // (never: the grid is nwork work-groups)
-  unsigned b = sx + (blockIdx.x >> 3);
+  unsigned b = patch_work_item(nwork, blockIdx.x);
+  if (b == PATCH_NO_ITEM) return;  // (never: the grid is nwork work-groups)
   const unsigned tiles_all = nwork / (unsigned)ksplit;
   // (the digits of a work item are wave-uniform; hipcc does the divisions on the VALU and then treats everything derived from them as divergent --
   // readfirstlane puts them, and the address arithmetic that follows, back on the scalar unit)
@@ -115,119 +113,41 @@ __global__ __launch_bounds__(512, 2) void conv_sk_kernel(const GmConvDesc p) {
   if (c_begin < c_end) issue_panels(c_begin, 0, FIRST);
   SK_STAMP(1);
 
-  // ---- the tile, and the patch rows of this lane (layouts of conv_dma.hip: rows of 64 bytes, the bank swizzle applied on the source side) ------
+  // ---- the tile, and the patch rows of this lane (direct input: host-checked) ---------------------------------------------------------------
   const int tw_i = __builtin_amdgcn_readfirstlane((int)(b % ntw)); b /= ntw;
   const int th_i = __builtin_amdgcn_readfirstlane((int)(b % nth)); b /= nth;
   const int td_i = __builtin_amdgcn_readfirstlane((int)(b % ntd)); b /= ntd;
   const int n = __builtin_amdgcn_readfirstlane((int)b);
   const int od0 = td_i * TD, oh0 = th_i * TH, ow0 = tw_i * TW;
-  int psw = 0, pvox[PPW];
-#pragma unroll
-  for (int j = 0; j < PPW; ++j) {
-    const int row = 16 * (wave + NW * j) + (lane >> 2);
-    const int pa = row / PLANE, rr = row - pa * PLANE;
-    const int pb = rr / PW, lc = rr - pb * PW;
-    psw |= dma_swz(lc) << (2 * j);
-    const int ud = od0 - p.pd + pa, uh = oh0 - p.ph + pb, uw = ow0 - p.pw + lc;
-    const bool ok = (row < PROWS) & (rr < PH * PW) & (ud >= 0) & (ud < p.Ds) & (uh >= 0) & (uh < p.Hs) & (uw >= 0) & (uw < p.Ws);
-    pvox[j] = ok ? ((n * p.Ds + ud) * p.Hs + uh) * p.Ws + uw : -1;
-  }
-  const char* xbase = reinterpret_cast<const char*>(p.x);
-  const char* x2base = reinterpret_cast<const char*>(p.x2);
-  const long long xrowb = p.x_ld * (long long)sizeof(T), x2rowb = p.x2_ld * (long long)sizeof(T);
-  const int nchunks0 = p.x2 ? p.cin_split / BK : nchunks;
+  int psw, pvox[PG::PPW];
+  patch_place<PG>(p, 0, n, od0, oh0, ow0, wave, lane, psw, pvox);
 
   const bool from_stats = PRE && p.pre_stats[0] != nullptr;  // (work-group uniform)
-  // [scale | shift] (PRE) and the patch pieces of a chunk
+  const bool arrays = PRE && !from_stats;
   auto issue_patch = [&](int chunk) __attribute__((always_inline)) {
-    if (PRE && !from_stats) {
-      const int nl = BK / 4;  // lanes 0 .. nl - 1 fetch the chunk's scale, nl .. 2 nl - 1 its shift (16 bytes each) into this wave's own copy
-      if (lane < 2 * nl) {
-        const float* src = (lane < nl ? p.pre_scale : p.pre_shift) + (long long)n * p.Cin + chunk * BK + 4 * (lane < nl ? lane : lane - nl);
-        dma16(src, lds0 + AFF_OFF + (unsigned)wave * AFF_WAVE);
-      }
-    }
-    const bool second = chunk >= nchunks0;  // wave-uniform: the chunk comes from x2 (virtual channel concatenation)
-    const char* cbase = second ? x2base + (long long)(chunk - nchunks0) * (BK * (int)sizeof(T)) : xbase + (long long)chunk * (BK * (int)sizeof(T));
-    const long long rowb = second ? x2rowb : xrowb;
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      if (wave + NW * j < PPIECES) {  // wave-uniform
-        // (both addresses computed, then selected: a conditional 64-bit multiply compiles to a branch per piece)
-        const char* in_src = cbase + (long long)(pvox[j] & ~(pvox[j] >> 31)) * rowb + (((lane & 3) ^ ((psw >> (2 * j)) & 3)) << 4);
-        const char* pad_src = zero + ((lane & 3) << 4);
-        dma16(pvox[j] >= 0 ? in_src : pad_src, lds0 + (unsigned)(16 * (wave + NW * j)) * DMA_ROWB);
-      }
-    }
+    patch_issue<T, PG>(p, arrays, chunk, n, pvox, psw, zero, lds0, (unsigned)AFF_OFF, wave, lane);
   };
-  // GroupNorm-apply + activation IN LDS on this wave's own landed pieces (conv_dma.hip: transform_patch; same arithmetic and rounding as gm_gn_apply)
-  auto transform_patch = [&](int chunk) __attribute__((always_inline)) {
-    float sc[VECW], sh[VECW];
-    // the wave's own copy of the chunk's (scale | shift), or the slice's table built from the statistics
-    const float* aff = from_stats ? reinterpret_cast<const float*>(smem + TAB_OFF) + (chunk - c_begin) * BK : reinterpret_cast<const float*>(smem + AFF_OFF + wave * AFF_WAVE);
-    const int shoff = from_stats ? TAB_CH : BK;
-#pragma unroll
-    for (int i = 0; i < VECW; i += 4) {
-      const float4 a = *reinterpret_cast<const float4*>(aff + (lane & 3) * VECW + i), c = *reinterpret_cast<const float4*>(aff + shoff + (lane & 3) * VECW + i);
-      sc[i] = a.x; sc[i + 1] = a.y; sc[i + 2] = a.z; sc[i + 3] = a.w;
-      sh[i] = c.x; sh[i + 1] = c.y; sh[i + 2] = c.z; sh[i + 3] = c.w;
-    }
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      if (wave + NW * j < PPIECES && pvox[j] >= 0) {
-        char* a = smem + (16 * (wave + NW * j) + (lane >> 2)) * DMA_ROWB + (((lane & 3) ^ ((psw >> (2 * j)) & 3)) << 4);
-        float v[VECW];
-        Vec16<T>::unpack(*reinterpret_cast<const uint4*>(a), v);
-#pragma unroll
-        for (int i = 0; i < VECW; ++i) v[i] = v[i] * sc[i] + sh[i];
-        conv_act_vec(v, p.pre_act, sizeof(T) == 4);
-        *reinterpret_cast<uint4*>(a) = Vec16<T>::pack(v);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-
   if (c_begin < c_end) {
     issue_patch(c_begin);
     issue_panels(c_begin, FIRST, NGROUPS);
   }
   SK_STAMP(2);
 
-  // ---- PRE from statistics (conv_sn.hip's recipe, the shared gn_short_* order: bit-identical to gm_gn_finalize_channels' short form): the channel sums of the groups
-  // this slice's channels belong to, then (scale, shift) of the slice's channels -- under the flight of the chunk's requests ------------------------------------------
+  // ---- PRE from statistics: (scale | shift) of the slice's channels from the channel sums of the whole groups they belong to (host-checked: at most COVER_CH
+  // channels) -- under the flight of the chunk's requests -------------------------------------------------------------------------------------------------------
   if (PRE && from_stats && c_begin < c_end) {
-    float* tab = reinterpret_cast<float*>(smem + TAB_OFF);
-    double* csum = reinterpret_cast<double*>(smem + CSUM_OFF);
     const int cpg = p.Cin / p.pre_groups;
     const int ch0 = c_begin * BK, ch1 = c_end * BK;
-    const int cov0 = (ch0 / cpg) * cpg, cov1 = min(p.Cin, ((ch1 - 1) / cpg + 1) * cpg);  // whole groups (host-checked: cov1 - cov0 <= COVER_CH)
-    const long long V = (long long)p.Ds * p.Hs * p.Ws;
-    for (int c = cov0 + tid; c < cov1; c += 64 * NW) {
-      const double2 v = gn_short_channel_sum(p.pre_stats[0], p.pre_S[0], p.pre_C[0], p.pre_stats[1], p.pre_S[1], p.pre_C[1], p.N, n, c);
-      csum[2 * (c - cov0)] = v.x; csum[2 * (c - cov0) + 1] = v.y;
-    }
-    __syncthreads();
-    for (int c = ch0 + tid; c < ch1; c += 64 * NW) {
-      const int g = c / cpg;
-      double a = 0.0, b2 = 0.0;
-      for (int j = 0; j < cpg; ++j) { a += csum[2 * (g * cpg + j - cov0)]; b2 += csum[2 * (g * cpg + j - cov0) + 1]; }
-      float sc1, sh1;
-      gn_short_scale_shift(a, b2, cpg, V, p.pre_eps, p.pre_gamma ? p.pre_gamma[c] : 1.f, p.pre_beta ? p.pre_beta[c] : 0.f, sc1, sh1);
-      tab[c - ch0] = sc1;
-      tab[TAB_CH + (c - ch0)] = sh1;
-    }
-    __syncthreads();
+    gn_short_table<64 * NW>(reinterpret_cast<float*>(smem + TAB_OFF), TAB_CH, reinterpret_cast<double*>(smem + CSUM_OFF), ch0, ch1, (ch0 / cpg) * cpg,
+                            min(p.Cin, ((ch1 - 1) / cpg + 1) * cpg), cpg, p.pre_stats[0], p.pre_S[0], p.pre_C[0], p.pre_stats[1], p.pre_S[1], p.pre_C[1], p.N, n,
+                            (long long)p.Ds * p.Hs * p.Ws, p.pre_eps, p.pre_gamma, p.pre_beta, tid);
   }
 
-  // ---- operand read addresses (conv_dma.hip: XADDR / WADDR) -----------------------------------------------------------------------------------
-  int xa[KS];
+  int xa[KS], wa0;
   {
     const int m0 = wave * MF * 16 + l15;
-    const int a = m0 >> 6, bb0 = (m0 >> 4) & 3, c = m0 & 15;
-#pragma unroll
-    for (int kw = 0; kw < KS; ++kw) xa[kw] = (a * PLANE + bb0 * PW + c + kw) * DMA_ROWB + ((q ^ dma_swz(c + kw)) << 4);
+    patch_operand_addresses<KS, PG>(m0 >> 6, (m0 >> 4) & 3, l15, q, PATCH_BYTES, xa, wa0);
   }
-  const int wa0 = PATCH_BYTES + l15 * DMA_ROWB + ((q ^ dma_swz(l15)) << 4);
 #define SK_XADDR(hk, kw) (xa[kw] + (hk) * (PW * DMA_ROWB))
 #define SK_WADDR(nf) (wa0 + (nf) * (16 * DMA_ROWB))
   f32x4_t acc[NFR][MF];
@@ -256,7 +176,10 @@ __global__ __launch_bounds__(512, 2) void conv_sk_kernel(const GmConvDesc p) {
     // the patch, this wave's scale / shift copy and panels 0 .. FIRST-1 have landed when only the AFTER_PATCH later panel instructions are in flight
     dma_wait<AFTER_PATCH>();
     if (chunk == c_begin) SK_STAMP(3);
-    if (PRE) transform_patch(chunk);
+    if (PRE) {  // the wave's own copy of the chunk's (scale | shift), or the slice's table built from the statistics
+      const float* aff = from_stats ? reinterpret_cast<const float*>(smem + TAB_OFF) + (chunk - c_begin) * BK : reinterpret_cast<const float*>(smem + AFF_OFF + wave * AFF_WAVE);
+      patch_transform<T, PG>(smem, aff, from_stats ? TAB_CH : BK, p.pre_act, pvox, psw, wave, lane);
+    }
     if (chunk == c_begin) SK_STAMP(4);
 #pragma unroll
     for (int tap = 0; tap < 27; ++tap) {
@@ -397,12 +320,8 @@ extern "C" int gm_conv_sk_eligible(const GmConvDesc* d) {
          d->sd == 1 && d->sh == 1 && d->sw == 1 && d->ltd == 2 && d->lth == 2 && d->ltw == 4 && (d->dtype == GM_F32 || d->dtype == GM_BF16) &&
          ((d->pre_stats[0] == nullptr && (d->pre_scale == nullptr || d->pre_shift != nullptr)) ||
           // the statistics form: short tables, whole groups, a slice's channels and their groups within the LDS tables
-          (d->pre_stats[0] != nullptr && d->pre_scale == nullptr && d->pre_shift == nullptr && d->pre_groups > 0 && d->Cin % d->pre_groups == 0 &&
-           d->pre_S[0] >= 1 && d->pre_S[0] <= GN_SHORT_MAX_ROWS && d->pre_C[0] > 0 &&
-           ((d->pre_stats[1] == nullptr && d->pre_C[1] == 0 && d->pre_C[0] == d->Cin) ||
-            (d->pre_stats[1] != nullptr && d->pre_S[1] >= 1 && d->pre_S[1] <= GN_SHORT_MAX_ROWS && d->pre_C[1] > 0 && d->pre_C[0] + d->pre_C[1] == d->Cin)) &&
-           (reinterpret_cast<uintptr_t>(d->pre_stats[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->pre_stats[1]) & 15) == 0 &&
-           sk_slice_channels(d) <= sk::TAB_CH && sk_slice_channels(d) + 2 * (d->Cin / d->pre_groups) <= sk::COVER_CH));
+          (d->pre_scale == nullptr && d->pre_shift == nullptr && gm_gn_stats_form_ok(d->pre_stats, d->pre_S, d->pre_C, d->Cin) && d->pre_groups > 0 &&
+           d->Cin % d->pre_groups == 0 && sk_slice_channels(d) <= sk::TAB_CH && sk_slice_channels(d) + 2 * (d->Cin / d->pre_groups) <= sk::COVER_CH));
 }
 
 template <typename T, bool PRE>

@@ -13,7 +13,7 @@
 // Same 4x4x16 tile, patch layout, source-side bank swizzle and packed weight image ([chunk][tap][Cout_pad][BK]) as conv_dma.hip / conv_sk.hip; also their
 // fused GroupNorm-apply + activation prologue in LDS (bit-identical arithmetic to gm_gn_apply), the second input source of a virtual concatenation and the
 // fused 1x1 shortcut.  bf16 and fp32.  Deterministic: fixed summation orders, statistics stored once per (tile, channel).
-#include "conv_dma_shared.h"
+#include "conv_patch.h"
 
 __device__ __attribute__((aligned(64))) unsigned int gm_sn_zero_row[16] = {0};  // the source of every padding row
 
@@ -28,7 +28,7 @@ template <int ND> struct Geom {
   static constexpr int TD = ND == 3 ? 4 : 1, TH = ND == 3 ? 4 : 16;
   static constexpr int PH = ND == 3 ? 6 : 18, PLANE = ND == 3 ? 112 : 336, PROWS = (ND == 3 ? 6 : 1) * PLANE, PPIECES = PROWS / 16;
   static constexpr int PATCH_BYTES = PROWS * DMA_ROWB, W_BYTES = NTAP * BN * DMA_ROWB;  // 43 008 + 27 648 (3-D), 21 504 + 9 216 (2-D)
-  static constexpr int AFF_OFF = PATCH_BYTES + W_BYTES, AFF_WAVE = 256;  // per wave: [scale | shift] of the chunk being staged (PRE, scale / shift arrays given)
+  static constexpr int AFF_OFF = PATCH_BYTES + W_BYTES, AFF_WAVE = PATCH_AFF_WAVE;  // per wave: [scale | shift] of the chunk being staged (PRE, scale / shift arrays given)
   static constexpr int MAX_CIN_TAB = 384;                                // ... or ONE table [scale[Cin] | shift[Cin]] built from the input's statistics (PRE, pre_stats),
   static constexpr int AFF_BYTES = 2 * MAX_CIN_TAB * 4 + MAX_CIN_TAB * 16;  //     behind it the per-channel fp64 (sum, sum of squares) the table is built from: 9 KiB
   static constexpr int STAT_OFF = AFF_OFF + AFF_BYTES;                   // [wave][16 channels][sum, sum of squares] fp32
@@ -56,21 +56,21 @@ template <typename T, bool PRE, int NW, int MF, int ND>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void conv_sn_kernel(const GmConvDesc p) {
   using namespace sn;
   typedef Geom<ND> GE;
-  constexpr int NTAP = GE::NTAP, TD = GE::TD, TH = GE::TH, PH = GE::PH, PLANE = GE::PLANE, PROWS = GE::PROWS, PPIECES = GE::PPIECES;
+  constexpr int NTAP = GE::NTAP, TD = GE::TD, TH = GE::TH, PH = GE::PH, PLANE = GE::PLANE, PROWS = GE::PROWS;
   constexpr int PATCH_BYTES = GE::PATCH_BYTES, AFF_OFF = GE::AFF_OFF, AFF_WAVE = GE::AFF_WAVE, STAT_OFF = GE::STAT_OFF, SKIP_ROUND = GE::SKIP_ROUND;
   static_assert(NW * MF * 16 == BM && NW <= MAXW && MF <= 4 && (ND == 2 || 4 % MF == 0), "waves x fragments cover the tile; a wave's fragments are lines of one plane");
-  constexpr int PPW = (PPIECES + NW - 1) / NW, WPW = (NTAP + NW - 1) / NW;  // patch / weight pieces per wave and chunk (tap = wave + NW h: one 1 KiB piece per tap)
+  typedef PatchGeom<NW, PLANE, PW, PH, PROWS> PG;
+  constexpr int WPW = (NTAP + NW - 1) / NW;  // weight pieces per wave and chunk (tap = wave + NW h: one 1 KiB piece per tap)
   // voxel m of the tile -> (plane, line, column): 3-D (m >> 6, (m >> 4) & 3, m & 15); 2-D (0, m >> 4, m & 15)
   auto m_plane = [](int m) { return ND == 3 ? m >> 6 : 0; };
   auto m_line = [](int m) { return ND == 3 ? (m >> 4) & 3 : m >> 4; };
   constexpr int BK = ConvTraits<T>::BK;
-  constexpr int VECW = ConvTraits<T>::VECW;
   extern __shared__ __attribute__((aligned(1024))) char smem[];  // [patch][27 taps x 16 weight rows][8 x (scale | shift)][8 x 16 statistic partials]
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, q = lane >> 4;
 
-  // ---- the work item: (tile, 16-channel block); XCD x owns a contiguous range, the blocks of a tile are neighbours in it (their patches meet in one L2) ----
+  // ---- the work item: (tile, 16-channel block); the blocks of a tile are neighbours in an XCD's range (their patches meet in one L2) ----
   // images, stride 2 (the Downsample convolution of a 2-D UNet, diffusion_model_unet.py:510-518): out(i, j) = the stride-1 result at (2 i, 2 j) -- the tiles walk
   // the STRIDE-1 grid of (2 Ho - 1) x (2 Wo - 1) positions and the epilogue stores the even ones (4x the MFMAs of a launch whose cost is its latency chain; the
   // generic kernel it replaces took 13 us and left the statistics to a stand-alone pass)
@@ -80,10 +80,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void conv_sn_kernel(const
   const int ncb = (p.Cout + BN - 1) / BN;
   const int nchunks = p.Cin / BK, cout_pad = (p.Cout + 15) & ~15;
   const unsigned nwork = (unsigned)p.N * ntd * nth * ntw * ncb;
-  const unsigned xcd = blockIdx.x & 7;
-  const unsigned q8 = nwork >> 3, r8 = nwork & 7, cx = q8 + (xcd < r8 ? 1u : 0u), sx = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  if ((blockIdx.x >> 3) >= cx) return;  // (never: the grid is nwork work-groups)
-  unsigned b = sx + (blockIdx.x >> 3);
+  unsigned b = patch_work_item(nwork, blockIdx.x);
+  if (b == PATCH_NO_ITEM) return;  // (never: the grid is nwork work-groups)
   const int cb = __builtin_amdgcn_readfirstlane((int)(b % ncb)); b /= ncb;
   const int tw_i = __builtin_amdgcn_readfirstlane((int)(b % ntw)); b /= ntw;
   const int th_i = __builtin_amdgcn_readfirstlane((int)(b % nth)); b /= nth;
@@ -105,102 +103,21 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void conv_sn_kernel(const
 
   issue_weights(0);  // (they need the channel block only: the patch placement arithmetic below runs under their flight)
 
-  // ---- patch rows of this lane (conv_dma.hip's layout: 64-byte rows, swizzle keyed on the row's column within its W line, applied on the source side) ----
-  int psw = 0, pvox[PPW];
-#pragma unroll
-  for (int j = 0; j < PPW; ++j) {
-    const int row = 16 * (wave + NW * j) + (lane >> 2);
-    const int pa = row / PLANE, rr = row - pa * PLANE;
-    const int pb = rr / PW, lc = rr - pb * PW;
-    psw |= dma_swz(lc) << (2 * j);
-    // in_mode 1: the input is the nearest-neighbour up-sampling by (fd, fh, fw) of the stored tensor, never materialised (reference Upsample,
-    // diffusion_model_unet.py:572-585): bounds on the virtual grid, source voxel = virtual / factor
-    int ud = od0 - p.pd + pa, uh = oh0 - p.ph + pb, uw = ow0 - p.pw + lc;
-    const int Dv = p.in_mode == 1 ? p.Ds * p.fd : p.Ds, Hv = p.in_mode == 1 ? p.Hs * p.fh : p.Hs, Wv = p.in_mode == 1 ? p.Ws * p.fw : p.Ws;
-    const bool ok = (row < PROWS) & (rr < PH * PW) & (ud >= 0) & (ud < Dv) & (uh >= 0) & (uh < Hv) & (uw >= 0) & (uw < Wv);
-    if (p.in_mode == 1) { ud /= p.fd; uh /= p.fh; uw /= p.fw; }
-    pvox[j] = ok ? ((n * p.Ds + ud) * p.Hs + uh) * p.Ws + uw : -1;
-  }
-  const char* xbase = reinterpret_cast<const char*>(p.x);
-  const char* x2base = reinterpret_cast<const char*>(p.x2);
-  const long long xrowb = p.x_ld * (long long)sizeof(T), x2rowb = p.x2_ld * (long long)sizeof(T);
-  const int nchunks0 = p.x2 ? p.cin_split / BK : nchunks;
+  int psw, pvox[PG::PPW];
+  patch_place<PG>(p, p.in_mode, n, od0, oh0, ow0, wave, lane, psw, pvox);
   const bool from_stats = PRE && p.pre_stats[0] != nullptr;  // (work-group uniform)
+  const bool arrays = PRE && !from_stats;
   auto issue_patch = [&](int chunk) __attribute__((always_inline)) {
-    if (PRE && !from_stats) {
-      const int nl = BK / 4;  // lanes 0 .. nl - 1 fetch the chunk's scale, nl .. 2 nl - 1 its shift (16 bytes each) into this wave's own copy
-      if (lane < 2 * nl) {
-        const float* src = (lane < nl ? p.pre_scale : p.pre_shift) + (long long)n * p.Cin + chunk * BK + 4 * (lane < nl ? lane : lane - nl);
-        dma16(src, lds0 + AFF_OFF + (unsigned)wave * AFF_WAVE);
-      }
-    }
-    const bool second = chunk >= nchunks0;  // wave-uniform: the chunk comes from x2 (virtual channel concatenation)
-    const char* cbase = second ? x2base + (long long)(chunk - nchunks0) * (BK * (int)sizeof(T)) : xbase + (long long)chunk * (BK * (int)sizeof(T));
-    const long long rowb = second ? x2rowb : xrowb;
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      if (wave + NW * j < PPIECES) {  // wave-uniform
-        const char* in_src = cbase + (long long)(pvox[j] & ~(pvox[j] >> 31)) * rowb + (((lane & 3) ^ ((psw >> (2 * j)) & 3)) << 4);
-        const char* pad_src = zero + ((lane & 3) << 4);
-        dma16(pvox[j] >= 0 ? in_src : pad_src, lds0 + (unsigned)(16 * (wave + NW * j)) * DMA_ROWB);
-      }
-    }
+    patch_issue<T, PG>(p, arrays, chunk, n, pvox, psw, zero, lds0, (unsigned)AFF_OFF, wave, lane);
   };
-  // GroupNorm-apply + activation IN LDS on this wave's own landed pieces (conv_dma.hip: transform_patch; same arithmetic and rounding as gm_gn_apply;
-  // rows that came from the zero page stay zero: the reference pads the ACTIVATED tensor)
-  auto transform_patch = [&](int chunk) __attribute__((always_inline)) {
-    float sc[VECW], sh[VECW];
-    // scale / shift of this lane's channel slot: the wave's own per-chunk copy, or the table over all input channels built from the statistics
-    const float* aff = reinterpret_cast<const float*>(smem + AFF_OFF) + (from_stats ? chunk * BK : wave * (AFF_WAVE / 4));
-    const int shoff = from_stats ? p.Cin : BK;
-#pragma unroll
-    for (int i = 0; i < VECW; i += 4) {
-      const float4 a = *reinterpret_cast<const float4*>(aff + (lane & 3) * VECW + i), c = *reinterpret_cast<const float4*>(aff + shoff + (lane & 3) * VECW + i);
-      sc[i] = a.x; sc[i + 1] = a.y; sc[i + 2] = a.z; sc[i + 3] = a.w;
-      sh[i] = c.x; sh[i + 1] = c.y; sh[i + 2] = c.z; sh[i + 3] = c.w;
-    }
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      if (wave + NW * j < PPIECES && pvox[j] >= 0) {
-        char* a = smem + (16 * (wave + NW * j) + (lane >> 2)) * DMA_ROWB + (((lane & 3) ^ ((psw >> (2 * j)) & 3)) << 4);
-        float v[VECW];
-        Vec16<T>::unpack(*reinterpret_cast<const uint4*>(a), v);
-#pragma unroll
-        for (int i = 0; i < VECW; ++i) v[i] = v[i] * sc[i] + sh[i];
-        conv_act_vec(v, p.pre_act, sizeof(T) == 4);
-        *reinterpret_cast<uint4*>(a) = Vec16<T>::pack(v);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-
   issue_patch(0);
 
-  // ---- PRE from statistics: scale[c] = rstd_g * gamma[c], shift[c] = beta[c] - mean_g * rstd_g * gamma[c] for every input channel, from the per-tile partials of
-  // the input's producer(s), under the flight of the first requests.  The SHORT-TABLE order of gm_gn_finalize_channels (groupnorm.hip: gn_short_* -- shared
-  // helpers, so the two are bit-identical): a thread owns a channel and adds its S <= GN_SHORT_MAX_ROWS rows in row order (fp64, eight loads in flight); a group is the sum of its
-  // channels in channel order.  A group may straddle the two sources of a virtual concatenation.
-  if (PRE && from_stats) {
-    float* tab = reinterpret_cast<float*>(smem + AFF_OFF);                                   // [scale[Cin] | shift[Cin]]
-    double* csum = reinterpret_cast<double*>(smem + AFF_OFF + 2 * GE::MAX_CIN_TAB * 4);      // [Cin][sum, sum of squares]
-    const int G = p.pre_groups, cpg = p.Cin / G;
-    const long long V = (long long)p.Ds * p.Hs * p.Ws;  // voxels of the NORMALISED tensor
-    for (int c = tid; c < p.Cin; c += 64 * NW) {
-      const double2 v = gn_short_channel_sum(p.pre_stats[0], p.pre_S[0], p.pre_C[0], p.pre_stats[1], p.pre_S[1], p.pre_C[1], p.N, n, c);
-      csum[2 * c] = v.x; csum[2 * c + 1] = v.y;
-    }
-    __syncthreads();
-    for (int c = tid; c < p.Cin; c += 64 * NW) {
-      const int g = c / cpg;
-      double a = 0.0, b2 = 0.0;
-      for (int j = 0; j < cpg; ++j) { a += csum[2 * (g * cpg + j)]; b2 += csum[2 * (g * cpg + j) + 1]; }
-      float sc1, sh1;
-      gn_short_scale_shift(a, b2, cpg, V, p.pre_eps, p.pre_gamma ? p.pre_gamma[c] : 1.f, p.pre_beta ? p.pre_beta[c] : 0.f, sc1, sh1);
-      tab[c] = sc1;
-      tab[p.Cin + c] = sh1;
-    }
-    __syncthreads();  // (transform_patch of chunk 0 runs in front of the first tap-loop barrier: the table needs its own)
-  }
+  // ---- PRE from statistics: the table [scale[Cin] | shift[Cin]] over every input channel, behind it the [Cin] fp64 channel sums it is built from -- under the
+  // flight of the first requests (its closing barrier: the prologue of chunk 0 runs in front of the first tap-loop barrier) ------------------------------------
+  if (PRE && from_stats)
+    gn_short_table<64 * NW>(reinterpret_cast<float*>(smem + AFF_OFF), p.Cin, reinterpret_cast<double*>(smem + AFF_OFF + 2 * GE::MAX_CIN_TAB * 4), 0, p.Cin, 0, p.Cin,
+                            p.Cin / p.pre_groups, p.pre_stats[0], p.pre_S[0], p.pre_C[0], p.pre_stats[1], p.pre_S[1], p.pre_C[1], p.N, n,
+                            (long long)p.Ds * p.Hs * p.Ws, p.pre_eps, p.pre_gamma, p.pre_beta, tid);
 
   // ---- the epilogue's per-channel addend (bias + shortcut bias + timestep row, this order, fp32) and this lane's output rows: under the first flight ----
   const int co4 = cb * BN + q * 4;  // this lane's four output channels (accumulator rows 4q .. 4q + 3 of the 16x16 MFMA)
@@ -229,15 +146,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void conv_sn_kernel(const
     }
   }
 
-  // ---- operand read addresses (conv_dma.hip: XADDR / WADDR) ---------------------------------------------------------------------------------------
-  int xa[KS];
-  {
-    const int m0 = wave * MF * 16 + l15;
-    const int a = m_plane(m0), bb0 = m_line(m0), c = m0 & 15;
-#pragma unroll
-    for (int kw = 0; kw < KS; ++kw) xa[kw] = (a * PLANE + bb0 * PW + c + kw) * DMA_ROWB + ((q ^ dma_swz(c + kw)) << 4);
-  }
-  const int wa0 = PATCH_BYTES + l15 * DMA_ROWB + ((q ^ dma_swz(l15)) << 4);
+  int xa[KS], wa0;
+  patch_operand_addresses<KS, PG>(m_plane(wave * MF * 16 + l15), m_line(wave * MF * 16 + l15), l15, q, PATCH_BYTES, xa, wa0);
   f32x4_t acc[MF];
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf) acc[mf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
@@ -252,7 +162,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void conv_sn_kernel(const
 
   for (int chunk = 0; chunk < nchunks; ++chunk) {
     dma_wait<0>();                    // this wave's pieces of the chunk (and, PRE, its scale / shift copy) have landed
-    if (PRE) transform_patch(chunk);
+    if (PRE) {  // the wave's own per-chunk copy of (scale | shift), or the table over all input channels built from the statistics
+      const float* aff = reinterpret_cast<const float*>(smem + AFF_OFF) + (from_stats ? chunk * BK : wave * (AFF_WAVE / 4));
+      patch_transform<T, PG>(smem, aff, from_stats ? p.Cin : BK, p.pre_act, pvox, psw, wave, lane);
+    }
     __builtin_amdgcn_s_barrier();     // ... everyone's
     read_tap(0, 0);
 #pragma unroll
@@ -429,19 +342,11 @@ extern "C" int gm_conv_sn_eligible(const GmConvDesc* d) {
           (d->pre_stats[0] == nullptr && d->pre_scale != nullptr && d->pre_shift != nullptr && (reinterpret_cast<uintptr_t>(d->pre_scale) & 15) == 0 &&
            (reinterpret_cast<uintptr_t>(d->pre_shift) & 15) == 0 && (d->Cin % 4) == 0) ||
           // the statistics form: short tables (their rows all sit in one wave of the fold), whole groups, the table over all input channels in LDS
-          (d->pre_stats[0] != nullptr && d->pre_scale == nullptr && d->pre_shift == nullptr && d->pre_groups > 0 && d->Cin % d->pre_groups == 0 &&
-           d->Cin <= sn::Geom<3>::MAX_CIN_TAB && d->pre_S[0] >= 1 && d->pre_S[0] <= GN_SHORT_MAX_ROWS && d->pre_C[0] > 0 &&
-           ((d->pre_stats[1] == nullptr && d->pre_C[1] == 0 && d->pre_C[0] == d->Cin) ||
-            (d->pre_stats[1] != nullptr && d->pre_S[1] >= 1 && d->pre_S[1] <= GN_SHORT_MAX_ROWS && d->pre_C[1] > 0 && d->pre_C[0] + d->pre_C[1] == d->Cin)) &&
-           (reinterpret_cast<uintptr_t>(d->pre_stats[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->pre_stats[1]) & 15) == 0 && d->in_mode == 0)) &&
-         (d->x2 == nullptr || (d->cin_split > 0 && d->cin_split < d->Cin && d->cin_split % bk == 0 && d->x2_ld % vecw == 0 &&
-                               (reinterpret_cast<uintptr_t>(d->x2) & 15) == 0)) &&
+          (d->pre_scale == nullptr && d->pre_shift == nullptr && gm_gn_stats_form_ok(d->pre_stats, d->pre_S, d->pre_C, d->Cin) && d->pre_groups > 0 &&
+           d->Cin % d->pre_groups == 0 && d->Cin <= sn::Geom<3>::MAX_CIN_TAB && d->in_mode == 0)) &&
+         gm_conv_second_source_ok(d, bk, vecw) && gm_conv_shortcut_ok(d, bk, vecw) &&
          // (any C_out / row pitch / alignment of y, res, bias, rowvec: four channels per lane go out as one vector where all of them allow it, element-wise otherwise)
-         (long long)d->N * d->Ds * d->Hs * d->Ws < (1LL << 31) && (long long)d->N * d->Do * d->Ho * d->Wo < (1LL << 31) &&
-         (!d->skip_x[0] ||
-          (d->skip_w && d->skip_cin[0] > 0 && d->skip_cin[0] % bk == 0 && d->skip_ld[0] % vecw == 0 && (reinterpret_cast<uintptr_t>(d->skip_x[0]) & 15) == 0 &&
-           (!d->skip_x[1] || (d->skip_cin[1] > 0 && d->skip_cin[1] % bk == 0 && d->skip_ld[1] % vecw == 0 &&
-                              (reinterpret_cast<uintptr_t>(d->skip_x[1]) & 15) == 0))));
+         (long long)d->N * d->Ds * d->Hs * d->Ws < (1LL << 31) && (long long)d->N * d->Do * d->Ho * d->Wo < (1LL << 31);
 }
 
 extern "C" long long gm_conv_sn_lds_bytes(int cfg) { return cfg == 25 ? sn::Geom<2>::LDS_BYTES : sn::Geom<3>::LDS_BYTES; }

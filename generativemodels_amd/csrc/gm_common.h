@@ -71,7 +71,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // ---- GroupNorm finalisation over SHORT statistic tables (every source S <= GN_SHORT_MAX_ROWS rows of [N][C_i][2] fp64 partials) -- shared by gm_gn_finalize_channels
-// (groupnorm.hip) and the consumer-side prologue of conv_sn.hip, which must agree bit for bit: a channel's partials are added in ROW order, a group is the sum
+// (groupnorm.hip) and the consumer-side prologues (gn_short_table below), which must agree bit for bit: a channel's partials are added in ROW order, a group is the sum
 // of its channels in CHANNEL order, everything in fp64.  Channel c of the concatenation (C0 + C1 channels) lives in source 0 when c < C0.
 #define GN_SHORT_MAX_ROWS 128  // (64 until the second half of round 6: the 32^3 level of a latent UNet leaves 128-row tables -- one partial per 256-voxel tile)
 __device__ __forceinline__ double2 gn_short_channel_sum(const double* s0, int S0, int C0, const double* s1, int S1, int C1, int N, int n, int c) {
@@ -103,6 +103,29 @@ __device__ __forceinline__ void gn_short_scale_shift(double a, double b, int cpg
   const double rstd = 1.0 / sqrt(var + (double)eps);
   scale = (float)(rstd * (double)gamma);
   shift = (float)((double)beta - mean * rstd * (double)gamma);
+}
+// The finalisation in a CONSUMER's prologue (conv_sn.hip, conv_sk.hip, token_gemm_wide_kernel), by all NT threads of a work-group, for sample n: the channel sums
+// of the whole groups [cov0, cov1) into csum[c - cov0] (a thread owns a channel: rows in row order), then scale / shift of channels [ch0, ch1) into
+// tab[c - ch0] / tab[sh_off + c - ch0] (a group = its channels' sums in channel order); a barrier behind each step.  V = voxels of the normalised tensor.
+// Only gn_short_channel_sum / gn_short_scale_shift do arithmetic here, in the order of gm_gn_finalize_channels' short form: the tables agree bit for bit.
+template <int NT>
+__device__ __forceinline__ void gn_short_table(float* tab, int sh_off, double* csum, int ch0, int ch1, int cov0, int cov1, int cpg, const double* s0, int S0, int C0,
+                                               const double* s1, int S1, int C1, int N, int n, long long V, float eps, const float* gamma, const float* beta, int tid) {
+  for (int c = cov0 + tid; c < cov1; c += NT) {
+    const double2 v = gn_short_channel_sum(s0, S0, C0, s1, S1, C1, N, n, c);
+    csum[2 * (c - cov0)] = v.x; csum[2 * (c - cov0) + 1] = v.y;
+  }
+  __syncthreads();
+  for (int c = ch0 + tid; c < ch1; c += NT) {
+    const int g = c / cpg;
+    double a = 0.0, b = 0.0;
+    for (int j = 0; j < cpg; ++j) { a += csum[2 * (g * cpg + j - cov0)]; b += csum[2 * (g * cpg + j - cov0) + 1]; }
+    float sc, sh;
+    gn_short_scale_shift(a, b, cpg, V, eps, gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f, sc, sh);
+    tab[c - ch0] = sc;
+    tab[sh_off + (c - ch0)] = sh;
+  }
+  __syncthreads();
 }
 
 static inline int gm_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

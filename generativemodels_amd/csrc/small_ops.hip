@@ -212,22 +212,8 @@ __global__ __launch_bounds__(256) void token_gemm_wide_kernel(const T* __restric
     float* tab = reinterpret_cast<float*>(gn_smem);
     double* csum = reinterpret_cast<double*>(gn_smem + 2 * (size_t)cin * 4);
     const int n = (blockIdx.y * 64) / ex.rows_per_sample;  // host: rows_per_sample % 64 == 0 -- one sample per work-group
-    const int cpg = cin / ex.gn_groups;
-    for (int c = threadIdx.x; c < cin; c += 256) {
-      const double2 v = gn_short_channel_sum(ex.gn_stats[0], ex.gn_S[0], ex.gn_C[0], ex.gn_stats[1], ex.gn_S[1], ex.gn_C[1], ex.gn_N, n, c);
-      csum[2 * c] = v.x; csum[2 * c + 1] = v.y;
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < cin; c += 256) {
-      const int g = c / cpg;
-      double a = 0.0, b2 = 0.0;
-      for (int j = 0; j < cpg; ++j) { a += csum[2 * (g * cpg + j)]; b2 += csum[2 * (g * cpg + j) + 1]; }
-      float sc1, sh1;
-      gn_short_scale_shift(a, b2, cpg, (long long)ex.rows_per_sample, ex.gn_eps, ex.gn_gamma ? ex.gn_gamma[c] : 1.f, ex.gn_beta ? ex.gn_beta[c] : 0.f, sc1, sh1);
-      tab[c] = sc1;
-      tab[cin + c] = sh1;
-    }
-    __syncthreads();
+    gn_short_table<256>(tab, cin, csum, 0, cin, 0, cin, cin / ex.gn_groups, ex.gn_stats[0], ex.gn_S[0], ex.gn_C[0], ex.gn_stats[1], ex.gn_S[1], ex.gn_C[1], ex.gn_N, n,
+                        (long long)ex.rows_per_sample, ex.gn_eps, ex.gn_gamma, ex.gn_beta, threadIdx.x);
   }
   if (r0 >= rows) return;  // wave-uniform
   const int row = r0 + l15;
@@ -780,10 +766,8 @@ extern "C" int gm_linear_rows_gn(const void* x, long long x_ld, const GmGnTables
                                  const void* res, long long res_ld, void* y, long long y_ld, int rows, int cin, int cout, int pre_act, int post_act, void* vt,
                                  int vt_c0, int vt_dh, int dtype, void* stream) {
   GM_REQUIRE(gn && gn->stats[0] && gn->groups > 0 && cin % gn->groups == 0 && cin <= 384, "GroupNorm tables: whole groups, at most 384 channels");
-  GM_REQUIRE(gn->S[0] >= 1 && gn->S[0] <= GN_SHORT_MAX_ROWS && gn->C[0] > 0 &&
-             ((gn->stats[1] == nullptr && gn->C[0] == cin) || (gn->stats[1] != nullptr && gn->S[1] >= 1 && gn->S[1] <= GN_SHORT_MAX_ROWS && gn->C[1] > 0 && gn->C[0] + gn->C[1] == cin)),
-             "short statistic tables covering the input channels");
-  GM_REQUIRE((reinterpret_cast<uintptr_t>(gn->stats[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(gn->stats[1]) & 15) == 0, "16-byte aligned tables");
+  const int gn_C[2] = {gn->C[0], gn->stats[1] ? gn->C[1] : 0};  // (C[1] is not read without a second source)
+  GM_REQUIRE(gm_gn_stats_form_ok(gn->stats, gn->S, gn_C, cin), "short, 16-byte aligned statistic tables covering the input channels");
   GM_REQUIRE(n_samples > 0 && rows_per_sample > 0 && rows_per_sample % 64 == 0 && rows == n_samples * rows_per_sample, "whole 64-row groups per sample");
   GM_REQUIRE(!vt || (dtype == GM_BF16 && vt_dh > 0 && vt_c0 >= 0 && vt_c0 < cout && (cout - vt_c0) % vt_dh == 0 && !res && post_act == 0), "the V^T image: bf16, whole heads, no residual");
   LinearRowsExtra ex = {};

@@ -785,6 +785,7 @@ GN_IN_CONSUMER = os.environ.get("GM_GN_IN_CONSUMER", "1") != "0"  # short statis
 GN_IN_TOKEN_GEMM = True  # ... and in the wide token GEMM (the q | k | v projection of an attention block)
 GN_IN_SPLIT_SLICES = True  # ... also in the K slices of a split launch (conv_sk.hip, second half of round 6)
 GN_IN_CONSUMER_MAX_ROWS = 128  # = GN_SHORT_MAX_ROWS of csrc/gm_common.h (64 until the 32^3 level's 128-row tables were measured)
+GN_IN_CONSUMER_MAX_CHANNELS = 384  # = sn::Geom::MAX_CIN_TAB of csrc/conv_sn.hip: the (scale | shift) table a consumer builds in LDS covers that many input channels
 
 
 class GnRecipe:
@@ -833,7 +834,7 @@ def gn_scale_shift_composed(x, groups: int, eps: float, gamma: Optional[torch.Te
         raise ValueError("num_channels must be divisible by num_groups")
     stats = [channel_stats(p) for p in parts]
     recipe = GnRecipe(stats, cs, n, v, groups, eps, gamma, beta, parts[0].device)
-    if GN_IN_CONSUMER and not torch.is_grad_enabled() and all(st.shape[0] <= GN_IN_CONSUMER_MAX_ROWS for st in stats) and c <= 384 and n > 0:
+    if GN_IN_CONSUMER and not torch.is_grad_enabled() and all(st.shape[0] <= GN_IN_CONSUMER_MAX_ROWS for st in stats) and c <= GN_IN_CONSUMER_MAX_CHANNELS and n > 0:
         return recipe
     return recipe.materialise()
 

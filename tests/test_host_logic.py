@@ -642,6 +642,89 @@ def test_native_planners_accept_and_reject_geometries_without_a_gpu():
     assert lib.gm_attention_stats_slots(C.byref(attn_desc(dh=80, q_ld=240, k_ld=240, v_ld=240, o_ld=80))) == 0  # not an LDS-DMA head dim
 
 
+def test_small_grid_convolutions_accept_and_reject_prologue_and_operand_forms_without_a_gpu():
+    """The host predicates of the small-grid LDS-DMA convolutions (gm_conv_lds_bytes: > 0 = takes the launch, -1 = does not): cfg 24 (3x3x3), cfg 25 (images
+    as depth-1 volumes) and the K slices of a split cfg 11 launch, through the forms of the GroupNorm prologue (none / scale + shift arrays / statistic tables of
+    one or two sources), the second input source and the fused shortcut -- every bound of the statistics form at its edge."""
+    import ctypes as C
+
+    from generativemodels_amd import _native as nat
+
+    lib = nat.lib()
+    SN3, SN2, DMA = 80896, 40960, 6 * 112 * 64 + 3 * 192 * 64 + 512   # LDS bytes of cfg 24 / cfg 25 / cfg 11
+
+    def lds(cin=64, **kw):
+        d = nat.GmConvDesc()
+        base = dict(N=1, Cin=cin, Cout=64, Ds=16, Hs=16, Ws=16, Do=16, Ho=16, Wo=16, kd=3, kh=3, kw=3, sd=1, sh=1, sw=1, pd=1, ph=1, pw=1,
+                    dd=1, dh=1, dw=1, in_mode=0, fd=1, fh=1, fw=1, dtype=1, ltd=2, lth=2, ltw=4, x_ld=cin, y_ld=64)
+        base.update(kw)
+        for k, v in base.items():
+            setattr(d, k, v)
+        d.x, d.y, d.w = 0x1000, 0x2000, 0x3000  # aligned dummies: the predicates only inspect them
+        return lib.gm_conv_lds_bytes(C.byref(d))
+
+    launches = {  # name -> (descriptor fields, LDS bytes when taken)
+        "cfg24": (dict(cfg=24), SN3),
+        "cfg25": (dict(cfg=25, kd=1, Ds=1, Do=1, pd=0, ltd=0, lth=4, ltw=4), SN2),
+        "cfg11 slices": (dict(cfg=11, ksplit=4, kpartial=0x8000), DMA),
+    }
+    arrays = dict(pre_scale=0x4000, pre_shift=0x5000, pre_act=1)
+
+    def stats(cin, c1=0, **kw):  # the statistics form: one source, or two with c1 channels in the second
+        return dict(dict(pre_stats=(0x6000, 0x7000 if c1 else 0), pre_S=(8, 16 if c1 else 0), pre_C=(cin - c1, c1), pre_groups=32, pre_eps=1e-5, pre_act=1), **kw)
+
+    for name, (geom, taken) in launches.items():
+        for cin in (64, 256):
+            def got(**kw):
+                return lds(cin, **dict(geom, **kw))
+
+            # accepted: no prologue, the arrays form, the statistics form with one and with two sources, row counts at the bound
+            assert got() == taken and got(**arrays) == taken, name
+            assert got(**stats(cin)) == taken and got(**stats(cin, 32)) == taken, name
+            assert got(**stats(cin, pre_S=(128, 0))) == taken and got(**stats(cin, 32, pre_S=(1, 128))) == taken, name
+            # rejected: a table of more than GN_SHORT_MAX_ROWS rows, or of none
+            assert got(**stats(cin, pre_S=(129, 0))) == -1 and got(**stats(cin, 32, pre_S=(8, 129))) == -1, name
+            assert got(**stats(cin, pre_S=(0, 0))) == -1 and got(**stats(cin, 32, pre_S=(8, 0))) == -1, name
+            # ... sources that do not add up to C_in; a second source without channels; channels without a second source
+            assert got(**stats(cin, 32, pre_C=(cin - 32, 64))) == -1 and got(**stats(cin, pre_C=(cin - 32, 0))) == -1, name
+            assert got(**stats(cin, 32, pre_C=(cin, 0))) == -1 and got(**stats(cin, pre_C=(cin - 32, 32))) == -1, name
+            # ... groups that do not divide C_in, or none
+            assert got(**stats(cin, pre_groups=48)) == -1 and got(**stats(cin, pre_groups=0)) == -1, name
+            # ... statistics and arrays together, or half of the arrays
+            assert got(**dict(stats(cin), **arrays)) == -1 and got(**dict(stats(cin), pre_scale=0x4000)) == -1, name
+            # ... a table that is not 16-byte aligned
+            assert got(**stats(cin, pre_stats=(0x6008, 0))) == -1 and got(**stats(cin, 32, pre_stats=(0x6000, 0x7008))) == -1, name
+
+            # the second input source: chunk-aligned split inside C_in, vector-aligned pitch and base
+            x2 = dict(x2=0x9000, x2_ld=64, cin_split=32)
+            assert got(**x2) == taken and got(**dict(x2, **stats(cin, 32))) == taken, name
+            assert got(**dict(x2, cin_split=48)) == -1 and got(**dict(x2, cin_split=0)) == -1 and got(**dict(x2, cin_split=cin)) == -1, name
+            assert got(**dict(x2, x2_ld=60)) == -1 and got(**dict(x2, x2=0x9008)) == -1, name
+            # the fused shortcut: packed weights, whole K chunks per part, vector-aligned pitches and bases
+            one = dict(skip_x=(0xA000, 0), skip_w=0xB000, skip_cin=(64, 0), skip_ld=(64, 0))
+            two = dict(skip_x=(0xA000, 0xC000), skip_w=0xB000, skip_cin=(64, 32), skip_ld=(64, 32))
+            assert got(**one) == taken and got(**two) == taken, name
+            assert got(**dict(one, skip_cin=(48, 0))) == -1 and got(**dict(two, skip_cin=(64, 48))) == -1 and got(**dict(two, skip_cin=(64, 0))) == -1, name
+            assert got(**dict(one, skip_w=0)) == -1 and got(**dict(one, skip_ld=(60, 0))) == -1 and got(**dict(two, skip_ld=(64, 60))) == -1, name
+            assert got(**dict(one, skip_x=(0xA008, 0))) == -1 and got(**dict(two, skip_x=(0xA000, 0xC008))) == -1, name
+
+    # each kernel's own table bounds.  cfg 24 / 25: the table over all input channels holds 384 of them
+    for geom, taken in (launches["cfg24"], launches["cfg25"]):
+        assert lds(384, **dict(geom, **stats(384))) == taken and lds(416, **dict(geom, **stats(416))) == -1
+        assert lds(416, **geom) == taken and lds(416, **dict(geom, **arrays)) == taken          # (the bound is the table's, not the kernel's)
+        assert lds(64, **dict(geom, in_mode=1, fd=1 if geom["cfg"] == 25 else 2, fh=2, fw=2, **arrays)) == taken  # the up-sampled input takes the arrays form only
+        assert lds(64, **dict(geom, in_mode=1, fd=1 if geom["cfg"] == 25 else 2, fh=2, fw=2, **stats(64))) == -1
+    # cfg 11 slices: a slice's channels within the 128-channel table, with the rest of their first and last group within 256 channels
+    geom, taken = launches["cfg11 slices"]
+    assert lds(512, **dict(geom, **stats(512))) == taken                                        # 4 slices of 128 channels, groups of 16
+    assert lds(1024, **dict(geom, **stats(1024))) == -1 and lds(1024, **geom) == taken          # 4 slices of 256 channels
+    assert lds(1024, **dict(geom, **arrays)) == taken and lds(1024, **dict(geom, ksplit=8, **stats(1024))) == taken
+    assert lds(512, **dict(geom, **stats(512, pre_groups=8))) == taken                          # 128 + 2 x 64 channels: at the bound
+    assert lds(512, **dict(geom, **stats(512, pre_groups=4))) == -1                             # 128 + 2 x 128
+    assert lds(256, **dict(geom, ksplit=0, kpartial=0, **stats(256))) == -1                     # not split: cfg 11 itself has no statistics form
+    assert lds(256, **dict(geom, ksplit=0, kpartial=0, **arrays)) == taken
+
+
 def test_training_api_has_no_cpu_fallback_and_checks_its_arguments():
     """generativemodels_amd.autograd / forward_train on CPU tensors raise (no eager fallback); argument checks run before any kernel."""
     from generativemodels_amd import autograd as A

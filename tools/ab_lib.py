@@ -1,6 +1,6 @@
 """GPU: one line of JSON for whatever library GM_NATIVE_LIB selects -- C2 forward time (10 forwards between HIP events), the per-label kernel
 sums of one profiled forward, and a digest of the output (variants of one kernel must agree bit for bit).
-usage: GM_NATIVE_LIB=$PWD/generativemodels_amd/lib/libgmamd_eb.so python tools/ab_lib.py [tag]"""
+usage: GM_NATIVE_LIB=$PWD/generativemodels_amd/lib/libgmamd_ablate.so python tools/ab_lib.py [tag]"""
 import hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
