@@ -150,6 +150,7 @@ PROTOTYPES = {
     "gm_transformer_decode_step": (C.c_int, [C.POINTER(GmDecodeDesc), c_vp]),
     "gm_transformer_decode_plan": (C.c_int, [C.POINTER(GmDecodeDesc), C.POINTER(C.c_int)]),
     "gm_embed_tokens": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
+    "gm_embed_positions_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_sample_probs": (C.c_int, [c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_sample_index": (C.c_int, [c_vp, c_ll, C.c_int, c_vp, c_vp, c_vp]),
     "gm_token_log_prob": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, C.c_int, C.c_int, c_vp]),
@@ -170,6 +171,9 @@ PROTOTYPES = {
     "gm_stats_colsum": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int, c_vp, C.c_int, c_vp]),
     "gm_attention_backward_workspace_bytes": (c_ll, [C.POINTER(GmAttnBwdDesc)]),
     "gm_attention_backward": (C.c_int, [C.POINTER(GmAttnBwdDesc), c_vp]),
+    "gm_attention_backward_causal_workspace_bytes": (c_ll, [C.POINTER(GmAttnBwdDesc)]),
+    "gm_attention_backward_causal": (C.c_int, [C.POINTER(GmAttnBwdDesc), c_vp]),
+    "gm_attention_backward_causal_walk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gm_attention_backward_fused_workspace_bytes": (c_ll, [C.POINTER(GmAttnBwdDesc)]),
     "gm_attention_backward_fused": (C.c_int, [C.POINTER(GmAttnBwdDesc), c_vp, c_vp]),
     "gm_attention_backward_fused_set_split": (None, [C.c_int]),

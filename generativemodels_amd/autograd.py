@@ -13,7 +13,9 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
                   routes, chosen from dtype, (sample, head) pairs, tokens and head dim by the table of attention_backward_route -- the fused
                   bf16 LDS-DMA flash backward, the bf16-MFMA score pass + weight-gradient kernels, the fused fp32 flash backward (head dims
                   zero-padded to 16 .. 256 for these two), or per (sample, head) in fp32 on the GEMM / weight-gradient kernels (the only one
-                  for head dims above 256, unpadded, up to 8192 tokens)
+                  for head dims above 256, unpadded, up to 8192 tokens); causal=True (the decoder-only transformer's mask): forward with the kernel's
+                  causal flag, backward always on the causal fp32-MFMA flash kernels (route "causal", head dims zero-padded to 16 .. 256)
+  embed_tokens    token + position embedding; both tables' gradients as fixed-order sums (gm_vq_ema_stats, gm_embed_positions_grad), no atomics
   resize          forward: F.interpolate (every mode) as one launch of the separable tap kernel; backward: the same kernel on the transposed tables
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
@@ -26,7 +28,7 @@ import torch
 
 from . import ops
 
-__all__ = ["cast", "scale", "leaky_relu", "kld", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["cast", "scale", "leaky_relu", "kld", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -447,15 +449,21 @@ def _route_flash(bf16, pairs, tokens, dh, dhp):
 _ATTENTION_BWD_ROUTES = ((_route_fused, "fused"), (_route_wide, "composed"), (_route_bf16, "bf16"), (_route_flash, "flash"), (lambda *shape: True, "composed"))
 
 
-def attention_backward_route(dtype, b: int, heads: int, lq: int, lk: int, dh: int, fused: bool = True):
+def attention_backward_route(dtype, b: int, heads: int, lq: int, lk: int, dh: int, fused: bool = True, causal: bool = False):
     """-> (route, dh_padded): which kernels differentiate attention over (b, lq | lk, heads * dh) operands of `dtype` -- "fused"
     (ops.attention_backward_fused), "bf16" (ops.attention_backward_bf16), "flash" (ops.attention_backward) or "composed"
-    (_attention_backward_composed) -- by the table above.  dh_padded != dh: a head dim the flash / bf16 kernels are not built for, every head
+    (_attention_backward_composed) -- by the table above.  causal=True (the forward's mask, query i sees keys j <= i + lk - lq): always
+    "causal" (ops.attention_backward_causal, the one masked backward: fp32-MFMA flash kernels for every dtype and length), head dims padded
+    like "flash"; ValueError above the widest built head (transformer heads are 8 to 64 wide).  dh_padded != dh: a head dim the flash / bf16 kernels are not built for, every head
     is zero-padded to that width first (never for "fused", whose head dims are built ones).  fused=False: the routes that remain when the
     library declines the fused kernels.  Plain integers and a dtype, no tensors, no library.  Raises ValueError for heads wider than the built
     kernels beyond ATTENTION_BWD_MAX_TOKENS."""
     widest = max(ops.ATTENTION_BWD_HEAD_DIMS)  # (= gm_attention_max_head_dim(): tests/test_attention_routes.py)
     dhp = dh if dh > widest or dh in ops.ATTENTION_BWD_HEAD_DIMS else min(d for d in ops.ATTENTION_BWD_HEAD_DIMS if d >= dh)
+    if causal:
+        if dh > widest:
+            raise ValueError(f"causal attention backward is built for head dims up to {widest} (got {dh})")
+        return "causal", dhp
     shape = (dtype == torch.bfloat16, b * heads, max(lq, lk), dh, dhp)
     for serves, route in _ATTENTION_BWD_ROUTES[0 if fused else 1:]:
         if serves(*shape):
@@ -474,31 +482,34 @@ def _fused_backward_serves(q, k, heads):
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale):
-        lse = None
-        if _fused_backward_serves(q, k, heads) and ops.attention_writes_lse(q, k, v, heads):
+    def forward(ctx, q, k, v, heads, scale, causal=False):
+        lse = None  # (causal: the LDS-DMA forward declines the mask, so no log-sum-exp is kept; the causal backward makes its own)
+        if not causal and _fused_backward_serves(q, k, heads) and ops.attention_writes_lse(q, k, v, heads):
             lse = torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device)  # the forward kernel's log-sum-exp: one sweep less in backward
-        o = ops.attention(q, k, v, heads, scale, lse_out=lse)
+        o = ops.attention(q, k, v, heads, scale, causal=causal, lse_out=lse)
         ctx.save_for_backward(q, k, v, o, *(() if lse is None else (lse,)))
-        ctx.cfg = (heads, scale)
+        ctx.cfg, ctx.causal = (heads, scale), causal
         return o
 
     @staticmethod
     def backward(ctx, go):
         q, k, v, o, *rest = ctx.saved_tensors
-        heads, scale = ctx.cfg
-        return (*attention_backward_by_route(q, k, v, o, go.contiguous(), heads, scale, lse=rest[0] if rest else None), None, None)
+        (heads, scale), causal = ctx.cfg, getattr(ctx, "causal", False)
+        return (*attention_backward_by_route(q, k, v, o, go.contiguous(), heads, scale, lse=rest[0] if rest else None, causal=causal), None, None, None)
 
 
-def attention_backward_by_route(q, k, v, o, go, heads, scale, lse=None, route=None):
+def attention_backward_by_route(q, k, v, o, go, heads, scale, lse=None, route=None, causal=False):
     """(dq, dk, dv) of o = softmax(scale q k^T) v over (B, L, heads * dh) operands: route (attention_backward_route), pad the heads if the route
     wants another width, dispatch, unpad.  lse: the forward kernel's log-sum-exp, for the fused kernels.  route: force one of the four (A/B
-    measurements: tools/) at the operands' own head dim -- its entry point raises when it does not serve them."""
+    measurements: tools/) at the operands' own head dim -- its entry point raises when it does not serve them.  causal: o was computed under the
+    forward's mask; the "causal" route is the only one that knows it."""
     b, lq, c = q.shape
     lk, dh = k.shape[1], c // heads
     forced, dhp = route is not None, dh
+    if causal and forced and route != "causal":
+        raise ValueError(f"attention backward route {route!r} does not know the causal mask")
     if not forced:
-        route, dhp = attention_backward_route(q.dtype, b, heads, lq, lk, dh)
+        route, dhp = attention_backward_route(q.dtype, b, heads, lq, lk, dh, causal=causal)
     if route == "fused":
         grads = ops.attention_backward_fused(q, k, v, o, go, heads, scale, lse=lse, or_none=not forced)
         if grads is not None:
@@ -520,8 +531,10 @@ def attention_backward_by_route(q, k, v, o, go, heads, scale, lse=None, route=No
         grads = _attention_backward_composed(q, k, v, go, heads, scale)
     elif route in ("bf16", "flash"):
         grads = (ops.attention_backward_bf16 if route == "bf16" else ops.attention_backward)(q, k, v, o, go, heads, scale)
+    elif route == "causal" and causal:
+        grads = ops.attention_backward_causal(q, k, v, o, go, heads, scale)
     else:
-        raise ValueError(f"attention backward route {route!r} is none of 'fused', 'bf16', 'flash', 'composed'")
+        raise ValueError(f"attention backward route {route!r} is none of 'fused', 'bf16', 'flash', 'composed' (or 'causal' for a causal forward)")
     return grads if dhp == dh else tuple(widen(g, dhp, dh) for g in grads)
 
 
@@ -555,9 +568,10 @@ def _attention_backward_composed(q, k, v, go, heads, scale):
     return dq, dk, dv
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
-    """softmax(scale Q K^T) V per (sample, head) over (B, L, heads * dh) operands; differentiable in q, k, v."""
-    return _Attention.apply(q, k, v, heads, scale)
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, causal: bool = False) -> torch.Tensor:
+    """softmax(scale Q K^T) V per (sample, head) over (B, L, heads * dh) operands; differentiable in q, k, v.  causal: query i sees keys
+    j <= i + (Lk - Lq) only (the decoder-only transformer's self-attention); its backward is the causal flash backward."""
+    return _Attention.apply(q, k, v, heads, scale, bool(causal))
 
 
 class _Add(torch.autograd.Function):
@@ -730,6 +744,29 @@ class _Embedding(torch.autograd.Function):
 def embedding(labels: torch.Tensor, weight: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """weight[labels] in `dtype` (default: the table's); differentiable in the table."""
     return _Embedding.apply(labels, weight, dtype)
+
+
+class _EmbedTokens(torch.autograd.Function):
+    """Token + absolute position embedding of the decoder-only transformer (transformer.py:99-101) with both tables' gradients: fixed-order sums
+    on native kernels (ops.embed_tokens_backward), not an atomic scatter -- a B * T-row index_add_ would not repeat its bits from step to step."""
+
+    @staticmethod
+    def forward(ctx, indices, token_weight, position_weight):
+        ctx.save_for_backward(indices)
+        ctx.tables = (token_weight.shape[0], token_weight.dtype, position_weight.shape[0], position_weight.dtype)
+        return ops.embed_tokens(indices, token_weight, position_weight, 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        (indices,) = ctx.saved_tensors
+        ntok, tdt, npos, pdt = ctx.tables
+        dtok, dpos = ops.embed_tokens_backward(indices, g.contiguous(), ntok, npos)
+        return None, dtok.to(tdt) if ctx.needs_input_grad[1] else None, dpos.to(pdt) if ctx.needs_input_grad[2] else None
+
+
+def embed_tokens(indices: torch.Tensor, token_weight: torch.Tensor, position_weight: torch.Tensor) -> torch.Tensor:
+    """token_weight[indices] + position_weight[arange(T)] for (B, T) int64 indices -> (B, T, C); differentiable in both tables."""
+    return _EmbedTokens.apply(indices, token_weight, position_weight)
 
 
 class _SpadeModulate(torch.autograd.Function):

@@ -52,6 +52,36 @@ extern "C" int gm_embed_tokens_dev(const long long* indices, const void* token_w
   GM_LAUNCH_CHECK();
 }
 
+// Gradient of the position table of gm_embed_tokens at pos0 = 0: out[t][c] = sum_b g[b][t][c] for t < T, in batch order (one thread per entry:
+// deterministic, no atomics), and 0 for the rows t >= T no token read.  fp32 [max_positions][C], whatever the storage dtype of g.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_positions_grad_kernel(const T* __restrict__ g, float* __restrict__ out, int batch, int T_len, int C,
+                                                                  int max_pos) {
+  const long long total = (long long)max_pos * C;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long t = i / C;
+    float acc = 0.f;
+    if (t < T_len)
+      for (int b = 0; b < batch; ++b) acc += ElemIO<T>::ld(g + (long long)b * T_len * C + i);
+    out[i] = acc;
+  }
+}
+
+extern "C" int gm_embed_positions_grad(const void* g, float* out, int batch, int seq_len, int C, int max_positions, int dtype, void* stream) {
+  GM_REQUIRE(out && (g || batch == 0), "null pointer");
+  GM_REQUIRE(batch >= 0 && seq_len > 0 && C > 0 && seq_len <= max_positions, "positions exceed the embedding table");
+  hipStream_t st = (hipStream_t)stream;
+  long long gr = ((long long)max_positions * C + 255) / 256;
+  if (gr > 4096) gr = 4096;
+  if (dtype == GM_F32)
+    embed_positions_grad_kernel<float><<<(int)gr, 256, 0, st>>>((const float*)g, out, batch, seq_len, C, max_positions);
+  else if (dtype == GM_BF16)
+    embed_positions_grad_kernel<bf16_raw><<<(int)gr, 256, 0, st>>>((const bf16_raw*)g, out, batch, seq_len, C, max_positions);
+  else
+    GM_FAIL(-2, "unsupported dtype");
+  GM_LAUNCH_CHECK();
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -553,7 +553,8 @@ class VQVAETransformerInferer(Inferer):
 
     def __call__(self, inputs: torch.Tensor, vqvae_model, transformer_model, ordering, condition: torch.Tensor | None = None,
                  return_latent: bool = False):
-        """Next-token logits for the (BOS-shifted) latent sequence of `inputs` (reference inferer.py:1134-1181)."""
+        """Next-token logits for the (BOS-shifted) latent sequence of `inputs` (reference inferer.py:1134-1181).  The training forward of the reference's
+        loop: the quantisation stays outside autograd, the transformer decides for itself (`_blocks.wants_grad`: differentiable logits in train() mode)."""
         with torch.no_grad():
             latent = vqvae_model.index_quantize(inputs)
         latent_spatial_dim = tuple(latent.shape[1:])

@@ -84,8 +84,26 @@ class SABlock(nn.Module):
         y = ops.attention(qkv[..., 0:c], cache["k"][:, :pos + 1], cache["v"][:, :pos + 1], self.num_heads, self.scale)
         return ops.linear(y, self.out_proj.weight, self.out_proj.bias, res=residual)
 
+    def run_train(self, x_norm: torch.Tensor, residual: Optional[torch.Tensor], context: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same block with gradients (generativemodels_amd.autograd): three projections, attention under the causal mask (its backward: the
+        causal flash kernels), out_proj with the residual in its epilogue."""
+        from ... import autograd as A
+
+        if self.dropout_rate > 0.0 and self.training:  # (DecoderOnlyTransformer builds its blocks with dropout_rate 0)
+            raise NotImplementedError("SABlock trains without dropout: the flash kernels have no dropout on the attention weights")
+        kv = x_norm if context is None else context
+        q = A.linear(x_norm, self.to_q.weight, self.to_q.bias)
+        k = A.linear(kv, self.to_k.weight, self.to_k.bias)
+        v = A.linear(kv, self.to_v.weight, self.to_v.bias)
+        y = A.attention(q, k, v, self.num_heads, self.scale, causal=self.causal and context is None)
+        return A.linear(y, self.out_proj.weight, self.out_proj.bias, res=residual)
+
     def forward(self, x: torch.Tensor, context: torch.Tensor | None = None) -> torch.Tensor:
+        from ..nets._blocks import wants_grad  # (the nets package imports this one)
+
         ops.require_device(x, context)
+        if wants_grad(self, x) or (context is not None and torch.is_grad_enabled() and context.requires_grad):
+            return self.run_train(x.contiguous(), None, None if context is None else context.contiguous())
         with torch.no_grad():
             zero = torch.zeros_like(x)
             return self.run(x.contiguous(), zero, None if context is None else context.contiguous())

@@ -26,6 +26,13 @@ class MLPBlock(nn.Module):
         a = ops.linear(x_norm, self.linear1.weight, self.linear1.bias, post_act="gelu")
         return ops.linear(a, self.linear2.weight, self.linear2.bias, res=residual)
 
+    def run_train(self, x_norm: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+        """The same block with gradients: the GELU is a pass of its own because its derivative is taken from the pre-activation."""
+        from ... import autograd as A
+
+        z = A.linear(x_norm, self.linear1.weight, self.linear1.bias)
+        return A.linear(A.activation(z, "gelu"), self.linear2.weight, self.linear2.bias, res=residual)
+
 
 class TransformerBlock(nn.Module):
     def __init__(self, hidden_size: int, mlp_dim: int, num_heads: int, dropout_rate: float = 0.0, qkv_bias: bool = False,
@@ -63,7 +70,21 @@ class TransformerBlock(nn.Module):
             x = self.cross_attn.run(self._ln(self.norm2, x), x, context)
         return self.mlp.run(self._ln(self.norm3, x), x)
 
+    def run_train(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same block with gradients (generativemodels_amd.autograd), native kernels in both directions."""
+        from ... import autograd as A
+
+        ln = lambda m, t: A.layer_norm(t, m.weight, m.bias, m.eps)  # noqa: E731
+        x = self.attn.run_train(ln(self.norm1, x), x)
+        if self.with_cross_attention:
+            x = self.cross_attn.run_train(ln(self.norm2, x), x, context)
+        return self.mlp.run_train(ln(self.norm3, x), x)
+
     def forward(self, x: torch.Tensor, context: torch.Tensor | None = None) -> torch.Tensor:
+        from ..nets._blocks import wants_grad  # (the nets package imports this one)
+
         ops.require_device(x, context)
+        if wants_grad(self, x) or (context is not None and torch.is_grad_enabled() and context.requires_grad):
+            return self.run_train(x.contiguous(), None if context is None else context.contiguous())
         with torch.no_grad():
             return self.run(x.contiguous(), None if context is None else context.contiguous())

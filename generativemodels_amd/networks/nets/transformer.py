@@ -17,6 +17,7 @@ import ctypes as C
 from ... import ops
 from ..._native import GmDecodeBlock, GmDecodeDesc, check, lib
 from ..blocks import TransformerBlock
+from ._blocks import wants_grad
 
 __all__ = ["DecoderOnlyTransformer", "AbsolutePositionalEmbedding"]
 
@@ -65,12 +66,42 @@ class DecoderOnlyTransformer(nn.Module):
     def forward(self, x: torch.Tensor, context: torch.Tensor | None = None) -> torch.Tensor:
         """(B, T) token indices -> (B, T, num_tokens) logits (reference transformer.py:98-106)."""
         self._check(x, context)
+        if wants_grad(self, x) or (context is not None and torch.is_grad_enabled() and context.requires_grad):
+            return self.forward_train(x, context)
         with torch.no_grad():
             h = ops.embed_tokens(x, self.token_embeddings.weight, self.position_embeddings.embedding.weight, 0)
             ctx = self._context(context)
             for blk in self.blocks:
                 h = blk.run(h, ctx)
             return ops.linear(h, self.to_logits.weight, self.to_logits.bias)
+
+    def supports_training(self) -> bool:
+        """forward_train covers every configuration this module builds (cross attention and embedding dropout included)."""
+        return True
+
+    def forward_train(self, x: torch.Tensor, context: torch.Tensor | None = None) -> torch.Tensor:
+        """The same forward with gradients, native kernels in both directions (generativemodels_amd.autograd): what the reference's training loop
+        differentiates -- logits = inferer(...), F.cross_entropy(logits.transpose(1, 2), target), loss.backward().  forward() selects it in
+        train() mode with gradients enabled and a trainable parameter, or for a context that requires grad (`_blocks.wants_grad`).  Mixed
+        precision as in DiffusionModelUNet.forward_train: the activations are stored in the compute dtype (the parameters', or the active autocast
+        region's over fp32 parameters), parameter gradients come back in the parameters' dtype."""
+        from ... import autograd as A
+
+        self._check(x, context)
+        pdtype = self.to_logits.weight.dtype
+        dtype = ops.compute_dtype(pdtype)
+        h = A.cast(A.embed_tokens(x.contiguous(), self.token_embeddings.weight, self.position_embeddings.embedding.weight), dtype)
+        drop = self.embedding_dropout
+        if drop.p > 0.0 and self.training:  # torch's own dropout op on the embedded tokens: the op, shape and generator the reference uses here
+            h = torch.nn.functional.dropout(h, p=drop.p, training=True)
+        ctx = None
+        if context is not None:
+            if context.dtype != dtype and ops.autocast_dtype() is None:
+                raise TypeError(f"context dtype {context.dtype} does not match the model dtype {pdtype}")
+            ctx = A.cast(context.contiguous(), dtype)
+        for blk in self.blocks:
+            h = blk.run_train(h, ctx)
+        return A.linear(h, self.to_logits.weight, self.to_logits.bias)
 
     # ---- incremental decoding ------------------------------------------------------------------------------------------------------
     def new_cache(self, batch: int, device) -> list:

@@ -1928,6 +1928,41 @@ def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: tor
     return dq, dk, dv
 
 
+def attention_backward_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, go: torch.Tensor, heads: int, scale: float,
+                              out: Optional[Sequence[torch.Tensor]] = None):
+    """(dq, dk, dv) of o = softmax(mask(scale q k^T)) v per (batch, head) under the forward's causal mask (attention(..., causal=True): query i sees
+    keys j <= i + Lk - Lq) by the causal flash backward (gm_attention_backward_causal): only the tiles that hold a visible pair are recomputed.
+    (B, L, heads * dh) operands (channel slices allowed), dh in ATTENTION_BWD_HEAD_DIMS, Lk >= Lq; more than 65 535 (sample, head) pairs go
+    through in groups of samples.  out: (dq, dk, dv) to write into -- batch-dense views shaped like q, k, v (any row pitch)."""
+    require_device(q, k, v, o, go, *(out or ()))
+    dh = q.shape[2] // heads
+    if dh not in ATTENTION_BWD_HEAD_DIMS:
+        raise ValueError(f"attention_backward_causal: head dim {dh} not in {ATTENTION_BWD_HEAD_DIMS}")
+    b, lq, lk, _ = _attn_bwd_dims(q, k, v, o, go, heads)
+    if lk < lq:
+        raise ValueError("causal attention needs at least as many keys as queries")
+    if heads > 65535:
+        raise ValueError("attention_backward_causal: more than 65535 heads")
+    if out is None:
+        dq, dk, dv = torch.empty_like(q.contiguous()), torch.empty_like(k.contiguous()), torch.empty_like(v.contiguous())
+    else:
+        dq, dk, dv = out
+        for g, t in ((dq, q), (dk, k), (dv, v)):
+            if g.shape != t.shape or g.dtype != t.dtype or (g.shape[0] > 1 and g.stride(0) != g.shape[1] * _kv_ld(g)):
+                raise ValueError("attention_backward_causal: out must be batch-dense (dq, dk, dv) shaped like q, k, v")
+    per = max(1, 65535 // heads)  # samples per launch: B * H <= 65535 (grid.y)
+    for s0 in range(0, b, per):
+        n = min(per, b - s0)
+        d = _attn_bwd_desc(q, k, v, o, go, heads, scale, grads=(dq, dk, dv), sample0=s0, samples=n)
+        ws = _attn_bwd_workspace(d, "gm_attention_backward_causal_workspace_bytes", q.device)  # noqa: F841 -- alive until the launch is enqueued
+        # visible pairs: Lq * (Lk - Lq) + Lq * (Lq + 1) / 2 of the Lq * Lk
+        pairs = float(lq) * (lk - lq) + 0.5 * lq * (lq + 1)
+        _timed(f"attention_bwd_causal<{str(q.dtype).split('.')[-1]}>",
+               dict(flops=14.0 * n * heads * pairs * dh, bytes=float(5 * q.element_size() * q.numel() * n / max(b, 1)), shape=f"B{n} H{heads} L{lq}x{lk} d{dh}"),
+               lambda: check(lib().gm_attention_backward_causal(C.byref(d), _stream()), "gm_attention_backward_causal"))
+    return dq, dk, dv
+
+
 ATTENTION_BWD_FUSED_HEAD_DIMS = (64, 128, 256)
 
 
@@ -2203,6 +2238,27 @@ def embed_tokens(indices: torch.Tensor, token_weight: torch.Tensor, position_wei
     check(lib().gm_embed_tokens(indices.data_ptr(), tw.data_ptr(), pw.data_ptr(), out.data_ptr(), b, t, tw.shape[1], int(pos0), tw.shape[0],
                                 pw.shape[0], dt_code(tw.dtype), _stream()), "gm_embed_tokens")
     return out
+
+
+def embed_tokens_backward(indices: torch.Tensor, g: torch.Tensor, num_tokens: int, max_positions: int):
+    """Gradients of embed_tokens(indices, token_weight, position_weight, 0) in its two tables from g = d(loss)/d(output) (B, T, C), fp32:
+    d token_weight[c] = sum of g[b, t] over the rows whose index is c -- the per-code vector sums of gm_vq_ema_stats (per-range partial tables
+    folded in range order) -- and d position_weight[t] = sum_b g[b, t] in batch order, rows >= T zero (gm_embed_positions_grad).  No atomics:
+    the same bits on every run."""
+    require_device(indices, g)
+    b, t = indices.shape
+    if g.dim() != 3 or tuple(g.shape[:2]) != (b, t) or indices.dtype != torch.long or t > max_positions:
+        raise ValueError("embed_tokens_backward expects (B, T) int64 indices and a (B, T, C) gradient with T inside the position table")
+    g, idx = g.contiguous(), indices.reshape(-1).contiguous()
+    c = g.shape[2]
+    stats = torch.empty(num_tokens + num_tokens * c, dtype=torch.float32, device=g.device)
+    work = torch.empty(max(1, int(lib().gm_vq_ema_stats_workspace_elems(idx.numel(), num_tokens, c))), dtype=torch.float32, device=g.device)
+    _timed("embed_tokens_bwd", dict(flops=0.0, bytes=float(g.element_size() * g.numel()), shape=f"B{b} T{t} C{c} V{num_tokens}"),
+           lambda: check(lib().gm_vq_ema_stats(g.data_ptr(), c, idx.data_ptr(), idx.numel(), num_tokens, c, stats.data_ptr(), work.data_ptr(),
+                                               dt_code(g.dtype), _stream()), "gm_vq_ema_stats"))
+    dpos = torch.empty((max_positions, c), dtype=torch.float32, device=g.device)
+    check(lib().gm_embed_positions_grad(g.data_ptr(), dpos.data_ptr(), b, t, c, max_positions, dt_code(g.dtype), _stream()), "gm_embed_positions_grad")
+    return stats[num_tokens:].view(num_tokens, c), dpos
 
 
 def sample_probs(logits: torch.Tensor, temperature: float, top_k: Optional[int], bos_index: int) -> torch.Tensor:

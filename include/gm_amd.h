@@ -313,6 +313,10 @@ int gm_attention_forward(const GmAttnDesc* d, void* stream);
 /* out[b][t][:] = token_weight[indices[b][t]] + position_weight[pos0 + t]  (transformer.py:99-101) */
 int gm_embed_tokens(const long long* indices, const void* token_weight, const void* position_weight, void* out, long long batch,
                     int seq_len, int C, int pos0, int num_tokens, int max_positions, int dtype, void* stream);
+/* gradient of the position table of gm_embed_tokens at pos0 = 0 (torch autograd through transformer.py:99-101): out[t][:] = sum_b g[b][t][:] in
+ * batch order for t < seq_len, 0 for the rows no token read; g: [batch][seq_len][C] in dtype, out: fp32 [max_positions][C].  (The token table's
+ * gradient is the per-code vector sum of gm_vq_ema_stats.)  Deterministic, no atomics. */
+int gm_embed_positions_grad(const void* g, float* out, int batch, int seq_len, int C, int max_positions, int dtype, void* stream);
 /* sampling head (inferer.py:1221-1232): probs = softmax(crop_topk(logits / temperature)), probs[:, bos_index] = 0; top_k <= 0: no crop.
  * logits: [rows][ld >= V] in dtype, probs: fp32 [rows][V] */
 int gm_sample_probs(const void* logits, long long ld, float* probs, long long rows, int V, float temperature, int top_k, int bos_index,
@@ -473,6 +477,15 @@ typedef struct GmAttnBwdDesc {
 } GmAttnBwdDesc;
 long long gm_attention_backward_workspace_bytes(const GmAttnBwdDesc* d);
 int gm_attention_backward(const GmAttnBwdDesc* d, void* stream);
+/* The same backward under the forward's causal mask (GmAttnDesc.causal: query i sees keys j <= i + Lk - Lq; torch autograd through
+ * blocks/selfattention.py:117-147): the same descriptor -- the entry point implies the mask -- and the same preconditions, plus Lk >= Lq.  The
+ * log-sum-exp is taken over the visible keys, a masked probability is exactly 0, and every work-group streams only the tiles that hold a
+ * visible pair for its rows (generativemodels_amd/csrc/attention_bwd_causal.hip). */
+long long gm_attention_backward_causal_workspace_bytes(const GmAttnBwdDesc* d);
+int gm_attention_backward_causal(const GmAttnBwdDesc* d, void* stream);
+/* The tile walk those kernels run, on the host: the work-group owning queries [64 block, ...) streams the 32-key tiles starting in
+ * [0, *key_end), the work-group owning keys [64 block, ...) the 32-query tiles starting in [*query_begin, Lq).  0 < Lq <= Lk.  No device call. */
+int gm_attention_backward_causal_walk(int Lq, int Lk, int block, int* key_end, int* query_begin);
 /* bf16-MFMA score pass of the attention backward (same autograd node as above; diffusion_model_unet.py:407-415): probs = softmax(scale Q K^T)
  * and dscores = probs (dO V^T - rowsum(dO O)) scale per (sample, head), bf16 [B*H][Lq][pd_ld] with pd_ld >= Lk rounded up to 64, plus
  * dscores_t = dscores^T as [B*H][Lk rounded up to 64][st_ld], st_ld >= Lq rounded up to 64 (padding written as zeros); bf16 operands, head
