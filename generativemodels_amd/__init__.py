@@ -27,7 +27,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 _MIRRORED = ["", ".networks", ".networks.nets", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",
-             ".inferers", ".utils", ".metrics"]
+             ".inferers", ".utils", ".metrics", ".losses"]
 
 
 def install_as_generative(force: bool = False) -> None:

@@ -87,6 +87,12 @@ class GmResizeDesc(C.Structure):
     _fields_ = [("n_in", C.c_int * 3), ("n_out", C.c_int * 3), ("start", c_vp * 3), ("index", c_vp * 3), ("weight", c_vp * 3)]
 
 
+class GmDftDesc(C.Structure):
+    _fields_ = [("src", c_vp), ("dst", c_vp), ("twiddle", c_vp), ("scale_dev", c_vp), ("src_stride", c_ll * 4), ("dst_stride", c_ll * 4),
+                ("extent", C.c_int * 4), ("src_axis_stride", c_ll), ("dst_axis_stride", c_ll), ("n", C.c_int), ("n_valid", C.c_int), ("n_store", C.c_int),
+                ("src_kind", C.c_int), ("dst_kind", C.c_int), ("inverse", C.c_int), ("scale", C.c_float), ("nstages", C.c_int), ("radix", C.c_int * 16)]
+
+
 # name -> (restype, argtypes); mirrors include/gm_amd.h one to one (tests/test_abi.py checks the export list)
 PROTOTYPES = {
     "gm_abi_version": (C.c_int, []),
@@ -199,6 +205,10 @@ PROTOTYPES = {
                              + [C.c_float, C.c_int, c_vp]),
     "gm_leaky_relu": (C.c_int, [c_vp, c_vp, c_vp, C.c_float, c_ll, C.c_int, c_vp]),
     "gm_kld": (C.c_int, [c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp]),
+    "gm_dft_max_length": (C.c_int, []),
+    "gm_dft_lines": (C.c_int, [C.POINTER(GmDftDesc), c_vp]),
+    "gm_spectral_loss_partials": (C.c_int, [c_ll]),
+    "gm_spectral_loss": (C.c_int, [c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_double, c_vp]),
 }
 
 _lib = None

@@ -898,3 +898,51 @@ class _Cast(torch.autograd.Function):
 
 def cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return x if x.dtype == dtype else _Cast.apply(x, dtype)
+
+
+class _SpectralLoss(torch.autograd.Function):
+    """JukeboxLoss (losses/spectral_loss.py:56-87): two forward transforms, the amplitude pass, and in the backward one adjoint transform per operand that
+    wants a gradient.  "sum" / "mean": the amplitude pass leaves the gradient spectra (for a unit upstream) over the operands' spectra; the upstream scalar
+    is read on the device by the adjoint's last pass.  "none": the spectra are kept and the backward forms the gradient spectra from the upstream map."""
+
+    @staticmethod
+    def forward(ctx, x, y, plan, reduction):
+        gx, gy = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ctx.plan, ctx.reduction, ctx.dtypes = plan, reduction, (x.dtype, y.dtype)
+        sx, sy = ops.dft_forward(x, plan), ops.dft_forward(y, plan)
+        if reduction == "none":
+            _, full, _, _ = ops.spectral_loss(sx, sy, plan, want_full=True)
+            if gx or gy:
+                ctx.save_for_backward(sx, sy)
+            return full
+        total = plan.batch * plan.count
+        value, _, hx, hy = ops.spectral_loss(sx, sy, plan, out_scale=1.0 / total if reduction == "mean" else 1.0, grad_x=gx, grad_y=gy, in_place=True)
+        ctx.save_for_backward(hx, hy)
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the backward is kernels, not torch ops: a second differentiation raises instead of returning no graph
+    def backward(ctx, g):
+        plan = ctx.plan
+        wx, wy = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g = g.to(torch.float32).contiguous()
+        if ctx.reduction == "none":
+            sx, sy = ctx.saved_tensors
+            _, _, hx, hy = ops.spectral_loss(sx, sy, plan, grad_x=wx, grad_y=wy, upstream=g)
+            scale, dev = 1.0, None
+        else:
+            hx, hy = ctx.saved_tensors
+            scale, dev = (1.0 / (plan.batch * plan.count) if ctx.reduction == "mean" else 1.0), g
+        return (ops.dft_adjoint(hx, plan, ctx.dtypes[0], scale, dev) if wx else None, ops.dft_adjoint(hy, plan, ctx.dtypes[1], scale, dev) if wy else None,
+                None, None)
+
+
+def spectral_loss(x: torch.Tensor, y: torch.Tensor, fft_signal_size=None, fft_norm: str = "ortho", reduction: str = "mean") -> torch.Tensor:
+    """(|fftn(x)| - |fftn(y)|)^2 over the channel axis and every spatial axis of two real (B, C, *spatial) tensors, fp32: the full (B, *s) map ("none"), its
+    sum or its mean; differentiable in x and y (a bin of amplitude zero contributes nothing to the gradient)."""
+    if x.shape != y.shape:
+        raise ValueError(f"spectral_loss: operands must share their shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError(f"spectral_loss: reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+    ops.require_device(x, y)
+    return _SpectralLoss.apply(x, y, ops.spectral_plan(x, fft_signal_size, fft_norm), reduction)

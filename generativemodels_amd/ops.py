@@ -17,8 +17,10 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native as nat
-from ._native import GmAttnBwdDesc, GmAttnDesc, GmConvDesc, GmGnTables, GmKlParams, GmResizeDesc, GmStepParams, GmWgradDesc, check, lib
+from ._native import GmAttnBwdDesc, GmAttnDesc, GmConvDesc, GmDftDesc, GmGnTables, GmKlParams, GmResizeDesc, GmStepParams, GmWgradDesc, check, lib
 from .resize_plan import ResizePlan, plan_for
+from .spectral_plan import SpectralPlan, device_twiddles
+from .spectral_plan import plan_for as spectral_plan_for
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 ACT = {"none": 0, "silu": 1, "relu": 2}
@@ -2634,3 +2636,103 @@ def mmd_terms(y: torch.Tensor, y_pred: torch.Tensor) -> torch.Tensor:
            lambda: check(lib().gm_mmd(y.data_ptr(), y_pred.data_ptr(), metric_dt_code(y.dtype), B, F, out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
                          "gm_mmd"))
     return out[0]
+
+
+# ---- generative.losses: Fourier transforms and the spectral loss (csrc/spectral.hip) ----------------------------------------------------------
+def dft_max_length() -> int:
+    """The longest axis gm_dft_lines transforms (what two LDS line buffers leave room for)."""
+    return int(lib().gm_dft_max_length())
+
+
+def _dft_pass(p, operands: dict, real_dtype: torch.dtype, scale: float = 1.0, scale_dev: Optional[torch.Tensor] = None) -> None:
+    src, dst = operands[p.src], operands[p.dst]
+    d = GmDftDesc()
+    d.src, d.dst, d.twiddle = src.data_ptr(), dst.data_ptr(), device_twiddles(p.n, src.device).data_ptr()
+    d.scale_dev = _ptr(scale_dev)
+    for a in range(4):
+        d.extent[a], d.src_stride[a], d.dst_stride[a] = p.extent[a], p.src_stride[a], p.dst_stride[a]
+    d.src_axis_stride, d.dst_axis_stride = p.src_axis_stride, p.dst_axis_stride
+    d.n, d.n_valid, d.n_store = p.n, p.n_valid, p.n_store
+    d.src_kind = metric_dt_code(real_dtype) if p.src_kind is None else p.src_kind
+    d.dst_kind = metric_dt_code(real_dtype) if p.dst_kind is None else p.dst_kind
+    d.inverse, d.scale, d.nstages = int(p.inverse), float(p.scale * scale), len(p.radices)
+    for i, r in enumerate(p.radices):
+        d.radix[i] = r
+    lines = math.prod(p.extent)
+    n_read = p.n // 2 + 1 if p.src_kind == 4 else p.n_valid
+    nbytes = lines * (n_read * (src.element_size() if p.src_kind is None else 8) + p.n_store * (dst.element_size() if p.dst_kind is None else 8))
+    _timed(f"dft_lines<{'inverse' if p.inverse else 'forward'} axis {p.axis}>", dict(flops=float(5 * lines * p.n * max(1, len(p.radices))), bytes=float(nbytes),
+                                                                                    shape=f"{lines}x{p.n}"),
+           lambda: check(lib().gm_dft_lines(C.byref(d), _stream()), "gm_dft_lines"))
+
+
+def spectral_plan(x: torch.Tensor, fft_signal_size=None, fft_norm: str = "ortho") -> SpectralPlan:
+    """The (cached) plan of fftn over the channel axis and every spatial axis of a (B, C, *spatial) tensor."""
+    return spectral_plan_for(tuple(x.shape), fft_signal_size, fft_norm)
+
+
+def dft_forward(x: torch.Tensor, plan: SpectralPlan) -> torch.Tensor:
+    """fftn(x, s, dim=(1, ..., -1), norm) of a real (B, C, *spatial) tensor (fp32, bf16 or fp16; a non-dense one is copied once) as its half spectrum:
+    (B, *m[:-1], m[-1] // 2 + 1, 2) fp32, the last axis (re, im)."""
+    require_device(x)
+    metric_dt_code(x.dtype)
+    if tuple(x.shape) != (plan.batch, *plan.n):
+        raise ValueError(f"dft_forward: the plan is for shape {(plan.batch, *plan.n)}, got {tuple(x.shape)}")
+    x = x.contiguous()
+    spec = torch.empty((*plan.spectrum_shape, 2), dtype=torch.float32, device=x.device)
+    for p in plan.forward:
+        _dft_pass(p, {"x": x, "spec": spec}, x.dtype)
+    return spec
+
+
+def dft_adjoint(h: torch.Tensor, plan: SpectralPlan, dtype: torch.dtype, scale: float = 1.0, scale_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of dft_forward applied to the half spectrum h (left unchanged): scale * scale_dev * norm_scale * Re(unnormalised inverse transform of the
+    Hermitian expansion of h), cropped or zero-filled to (B, C, *spatial), in `dtype`.  scale_dev: one fp32 value on the device, or None."""
+    require_device(h, scale_dev)
+    metric_dt_code(dtype)
+    if tuple(h.shape) != (*plan.spectrum_shape, 2) or h.dtype != torch.float32 or not h.is_contiguous():
+        raise ValueError(f"dft_adjoint: expected a dense fp32 half spectrum {(*plan.spectrum_shape, 2)}, got {tuple(h.shape)} {h.dtype}")
+    if scale_dev is not None and (scale_dev.numel() != 1 or scale_dev.dtype != torch.float32):
+        raise ValueError("dft_adjoint: the device scale is one fp32 value")
+    shape = (plan.batch, *plan.n)
+    out = (torch.zeros if plan.crops else torch.empty)(shape, dtype=dtype, device=h.device)  # entries beyond a cropped axis are written by no pass
+    operands = {"h": h, "x": out}
+    if len(plan.adjoint) > 1:
+        operands["work"] = torch.empty_like(h)
+    for p in plan.adjoint:
+        last = p.dst == "x"
+        _dft_pass(p, operands, dtype, scale if last else 1.0, scale_dev if last else None)
+    return out
+
+
+def spectral_loss(x: torch.Tensor, y: torch.Tensor, plan: SpectralPlan, *, out_scale: Optional[float] = None, want_full: bool = False,
+                  grad_x: bool = False, grad_y: bool = False, in_place: bool = False, upstream: Optional[torch.Tensor] = None):
+    """(|x| - |y|)^2 over two half spectra of dft_forward.  out_scale: the reduced value out_scale * sum over the full spectrum as an fp32 scalar;
+    want_full: the (B, *m) fp32 map (its own launch); grad_x / grad_y: the spectra of the gradients, for a unit upstream or the (B, *m) fp32 map
+    `upstream`, written over x / y when in_place.  -> (value, full, hx, hy), None where not asked for."""
+    require_device(x, y, upstream)
+    want = (*plan.spectrum_shape, 2)
+    for t in (x, y):
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"spectral_loss: expected dense fp32 half spectra {want}, got {tuple(t.shape)} {t.dtype}")
+    if want_full and (grad_x or grad_y):
+        raise ValueError("spectral_loss: the full map and the gradient spectra are separate calls")
+    if upstream is not None and (tuple(upstream.shape) != plan.full_shape or upstream.dtype != torch.float32 or not upstream.is_contiguous()):
+        raise ValueError(f"spectral_loss: the upstream map is a dense fp32 {plan.full_shape} tensor")
+    if out_scale is None and not (want_full or grad_x or grad_y):
+        raise ValueError("spectral_loss: nothing asked for")
+    bins = math.prod(plan.spectrum_shape)
+    value = partials = full = None
+    if out_scale is not None:
+        value = torch.empty((), dtype=torch.float32, device=x.device)
+        partials = torch.empty((int(lib().gm_spectral_loss_partials(bins)),), dtype=torch.float64, device=x.device)
+    if want_full:
+        full = torch.empty(plan.full_shape, dtype=torch.float32, device=x.device)
+    hx = (x if in_place else torch.empty_like(x)) if grad_x else None
+    hy = (y if in_place else torch.empty_like(y)) if grad_y else None
+    m = (1,) * (4 - len(plan.m)) + tuple(plan.m)
+    nbytes = 8 * bins * (2 + int(grad_x) + int(grad_y)) + (4 * math.prod(plan.full_shape) if want_full or upstream is not None else 0)
+    _timed("spectral_loss", dict(flops=float(12 * bins), bytes=float(nbytes), shape=str(plan.spectrum_shape)),
+           lambda: check(lib().gm_spectral_loss(x.data_ptr(), y.data_ptr(), plan.batch, m[0], m[1], m[2], m[3], _ptr(upstream), _ptr(hx), _ptr(hy), _ptr(full),
+                                                _ptr(partials), _ptr(value), float(out_scale or 0.0), _stream()), "gm_spectral_loss"))
+    return value, full, hx, hy

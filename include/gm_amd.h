@@ -571,6 +571,47 @@ int gm_leaky_relu(const void* x, const void* gy, void* out, float slope, long lo
  * neither, dtype of mu) = up * mu and up * -0.5 * (1 - exp(logvar)), `up` = upstream[0] read on the device (NULL: 1). */
 int gm_kld(const void* mu, const void* logvar, long long total, float* out, const float* upstream, void* dmu, void* dlogvar, int dtype, void* stream);
 
+/* ---- Fourier transforms and the spectral loss (losses/spectral_loss.py) ------------------------------------------------------
+ * One pass of 1-D discrete Fourier transforms over a grid of lines, mixed-radix Stockham autosort in LDS, fp32 arithmetic.  A transform over several axes
+ * is a sequence of these passes made by the host planner (generativemodels_amd/spectral_plan.py), which also supplies the radices (their product is n;
+ * 2, 3, 4, 5 have dedicated butterflies, any other prime a direct one) and the DEVICE twiddle table exp(-2 pi i j / n), j < n, as fp32 pairs.
+ * Element kinds: GM_F32 / GM_BF16 / GM_F16 real, 3 complex fp32, 4 (source only) complex fp32 lines that hold the n / 2 + 1 bins of a Hermitian
+ * spectrum and are expanded to n points on load.  A line reads its first n_valid points (the rest is zero), transforms n, stores its first n_store
+ * outputs times scale (times scale_dev[0] when given): complex, or the real part in a real kind.  Line (i0, i1, i2, i3) of the grid `extent` (i3
+ * fastest) starts at sum(i * stride) elements; consecutive points are src_axis_stride / dst_axis_stride elements apart.  src == dst is allowed
+ * when the lines do not overlap.  n is at most gm_dft_max_length(): what two line buffers leave room for in the 160 KiB of LDS. */
+typedef struct GmDftDesc {
+  const void* src;
+  void* dst;
+  const float* twiddle;
+  const float* scale_dev;
+  long long src_stride[4];
+  long long dst_stride[4];
+  int extent[4];
+  long long src_axis_stride;
+  long long dst_axis_stride;
+  int n;
+  int n_valid;
+  int n_store;
+  int src_kind;
+  int dst_kind;
+  int inverse;
+  float scale;
+  int nstages;
+  int radix[16];
+} GmDftDesc;
+int gm_dft_max_length(void);
+int gm_dft_lines(const GmDftDesc* d, void* stream);
+/* JukeboxLoss over two half spectra x, y: (batch, m0, m1, m2, n_last / 2 + 1) complex fp32 (missing leading axes: 1), v = (|x| - |y|)^2 per bin.
+ *   out (with partials: gm_spectral_loss_partials(bins) doubles, bins = the complex count of x)   out[0] = out_scale * the sum of v over the FULL spectrum
+ *       (a bin counts twice unless its last index is 0 or n_last / 2): per work-group partials and a fixed-order fold, no atomics
+ *   full   (batch, m0, m1, m2, n_last) fp32: v at every bin and at its mirror (-k mod m), mirrored pairs equal bit for bit
+ *   hx, hy (either, both or neither; hx may be x and hy may be y)   the spectra of the gradients: u * 2 (|x| - |y|) x / |x| and u * 2 (|y| - |x|) y / |y|,
+ *       0 where the amplitude is 0; u = 1, or with `upstream` (the shape of full) the mean of upstream at the bin and at its mirror */
+int gm_spectral_loss_partials(long long bins);
+int gm_spectral_loss(const float* x, const float* y, long long batch, int m0, int m1, int m2, int n_last, const float* upstream, float* hx, float* hy,
+                     float* full, double* partials, float* out, double out_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
