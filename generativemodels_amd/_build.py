@@ -14,12 +14,15 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libgmamd.so")
 OBJDIR = os.path.join(HERE, "build")
+# the public header: the kernels are compiled against it (csrc/gm_common.h includes it), so it is the one definition of every struct and prototype
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+PUBLIC_HEADER = os.path.join(INCLUDE, "gm_amd.h")
 # "file.hip#k": the file compiled with -DGM_DMA_PART=k into its own object (conv_dma.hip: 26 kernel instantiations, 4.5 minutes as one
 # translation unit -- five parts build in parallel)
 SOURCES = ["capi.cpp", "elementwise.hip", "groupnorm.hip", "conv.hip", "conv_fast.hip", "conv_dma.hip#1", "conv_dma.hip#0", "conv_dma.hip#2", "conv_dma.hip#3",
            "conv_dma.hip#4", "conv_sk.hip", "conv_sn.hip", "conv_edge.hip", "attention.hip", "attention_wide.hip", "attention_dma.hip", "attention_bwd.hip", "attention_bwd_causal.hip", "attention_bwd_dma.hip", "transformer_ops.hip", "decode_step.hip", "small_ops.hip", "backward.hip", "vq.hip", "metrics.hip", "spade_net.hip", "resize.hip", "spectral.hip"]
 ARCH = "gfx950"
-FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"]
+FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result", f"-I{INCLUDE}"]
 
 
 def hip_runtime_library() -> str:
@@ -75,7 +78,7 @@ def _compile(src: str) -> str:
         src, part = src.split("#")
     obj = os.path.join(OBJDIR if _variant is None else OBJDIR + "_" + _variant, os.path.splitext(src)[0] + ("" if part is None else f"_p{part}") + ".o")
     srcp = os.path.join(CSRC, src)
-    deps = [srcp, os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    deps = [srcp, os.path.abspath(__file__), PUBLIC_HEADER] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     if _stale(obj, deps):
         extra = os.environ.get("GM_EXTRA_HIPCC_FLAGS", "").split() + (VARIANTS[_variant] if _variant else []) + ([] if part is None else [f"-DGM_DMA_PART={part}"])
         if _variant == "asan" and src in ASAN_PLAIN:  # (still built for gfx950:xnack+ so that the library loads as one code object family)

@@ -93,7 +93,8 @@ class GmDftDesc(C.Structure):
                 ("src_kind", C.c_int), ("dst_kind", C.c_int), ("inverse", C.c_int), ("scale", C.c_float), ("nstages", C.c_int), ("radix", C.c_int * 16)]
 
 
-# name -> (restype, argtypes); mirrors include/gm_amd.h one to one (tests/test_abi.py checks the export list)
+# name -> (restype, argtypes); mirrors include/gm_amd.h one to one (tests/test_abi.py holds every name, argument and return type, and the layout of
+# every struct above, to the header)
 PROTOTYPES = {
     "gm_abi_version": (C.c_int, []),
     "gm_last_error": (C.c_char_p, []),

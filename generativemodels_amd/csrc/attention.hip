@@ -359,8 +359,6 @@ static int dispatch_attn(const GmAttnDesc& d, hipStream_t st) {
 }
 
 extern "C" int gm_attention_max_head_dim(void) { return GM_ATTN_MAX_DH; }
-extern "C" int gm_attention_dma_try(const GmAttnDesc* dp, void* stream);     // attention_dma.hip
-extern "C" int gm_attention_decode_try(const GmAttnDesc* dp, void* stream);  // small_ops.hip
 
 extern "C" int gm_attention_forward(const GmAttnDesc* dp, void* stream) {
   GM_REQUIRE(dp, "null descriptor");

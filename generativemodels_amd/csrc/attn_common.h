@@ -1,4 +1,5 @@
-// Attention descriptor shared by attention.hip (register-staged, any dtype / head dim) and attention_dma.hip (bf16, LDS-DMA).
+// Pieces shared by the attention kernels (GmAttnDesc / GmAttnBwdDesc themselves: include/gm_amd.h): attention.hip (register-staged, any dtype / head dim),
+// attention_dma.hip (bf16, LDS-DMA), attention_wide.hip, the backward files and the decode step's kernels in small_ops.hip.
 #pragma once
 #include "gm_common.h"
 
@@ -7,41 +8,6 @@
 // widest head the register-staged kernels serve in one pass (attention.hip), and the widest the sliced kernel serves (attention_wide.hip)
 #define GM_ATTN_MAX_DH 256
 #define GM_ATTN_WIDE_MAX_DH 1024
-
-struct GmAttnDesc {
-  const void* q; long long q_ld;
-  const void* k; long long k_ld;
-  const void* v; long long v_ld;
-  const void* res; long long res_ld;  // optional residual, same geometry as o
-  void* o; long long o_ld;
-  int B, H, Lq, Lk, dh;
-  float scale;
-  int dtype;
-  void* workspace;             // optional scratch (gm_attention_workspace_bytes): enables the LDS-DMA kernel
-  long long workspace_bytes;
-  int causal;                  // 1: query i attends keys j <= i + (Lk - Lq) only (SABlock causal mask, blocks/selfattention.py:133-134)
-  long long k_bs, v_bs;        // batch strides of k / v in elements; 0 = dense (Lk * ld).  A KV cache is [B][max_len][C] read up to Lk.
-  double* stats;               // optional [gm_attention_stats_slots][B][H * dh][2] per-channel (sum, sum of squares) partials of the stored output
-  int vt_packed;               // 1: the workspace already holds the transposed V image (written by gm_linear_rows_affine_vt): no pack launch
-  float* lse;                  // optional [B*H][Lq] fp32: log sum_k exp(scale q.k), written by the LDS-DMA path only (the training forward keeps it for
-                               // gm_attention_backward_fused)
-};
-
-// Attention backward descriptor (attention_bwd.hip: fp32-MFMA fused kernels and the bf16 score pass; attention_bwd_dma.hip: fused bf16 LDS-DMA kernels)
-struct GmAttnBwdDesc {
-  const void* q; long long q_ld;
-  const void* k; long long k_ld;
-  const void* v; long long v_ld;
-  const void* o; long long o_ld;       // forward output WITHOUT the residual
-  const void* go; long long go_ld;     // gradient of the forward output
-  void* dq; long long dq_ld;
-  void* dk; long long dk_ld;
-  void* dv; long long dv_ld;
-  int B, H, Lq, Lk, dh;
-  float scale;
-  int dtype;
-  void* workspace; long long workspace_bytes;  // gm_attention_backward_workspace_bytes / gm_attention_backward_fused_workspace_bytes
-};
 
 #ifdef __HIPCC__
 // 256 < dh <= GM_ATTN_WIDE_MAX_DH, fp32 / bf16, after gm_attention_forward's descriptor checks (attention_wide.hip); 0 = launched

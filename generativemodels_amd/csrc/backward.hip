@@ -19,19 +19,6 @@
 // reduces the splits in a fixed order (deterministic, no atomics) into the nn.ConvNd weight layout.
 #include "conv_common.h"
 
-struct GmWgradDesc {
-  const void* x; long long x_ld;      // [N][Ds][Hs][Ws][Cin]
-  const void* gy; long long gy_ld;    // [N][Do][Ho][Wo][Cout]
-  float* dw;                          // fp32 [Cout][Cin][kd][kh][kw]
-  void* workspace; long long workspace_bytes;
-  int N, Cin, Cout, Ds, Hs, Ws, Do, Ho, Wo;
-  int kd, kh, kw;                     // 1 or 3 per axis; kh == kw
-  int stride;                         // 1 or 2, every axis (depth too when kd == 3)
-  int pd, ph, pw;                     // low-side padding
-  int dtype;                          // of x and gy
-  int accumulate;                     // 0: dw is overwritten, 1: added to
-};
-
 static constexpr int wg_pad_pitch(int bytes) { return ((bytes - 16 + 255) / 256) * 256 + 16; }  // smallest >= bytes that is 16 mod 256
 
 template <typename T> struct WgTraits;

@@ -355,23 +355,15 @@ static const ConvCfg kCfgs[] = {
 static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
 // fast stride-1 path (conv_fast.hip): cfg 5 = 256 voxels x 64 channels, cfg 6 = 256 voxels x 128 channels
-extern "C" long long gm_conv_fast_lds_bytes(const GmConvDesc* d, int bn);
-extern "C" long long gm_conv_fast_max_patch(int wn);
-extern "C" int gm_conv_fast_launch(const GmConvDesc* dp, int wn, unsigned nblocks, void* stream);
 #define CONV_CFG_FAST64 5
 #define CONV_CFG_FAST128 6
 #define CONV_CFG_FAST_LAST 10
-extern "C" int gm_conv_fast_variant_geometry(int variant, int* voxels, int* channels, int* threads);
 static inline bool conv_is_fast(int cfg) { return cfg >= CONV_CFG_FAST64 && cfg <= CONV_CFG_FAST_LAST; }
 static inline int conv_fast_variant(int cfg) { return cfg - CONV_CFG_FAST64 + 1; }
 static inline int conv_fast_bn(int cfg) { int v = 0, c = 0, t = 0; gm_conv_fast_variant_geometry(conv_fast_variant(cfg), &v, &c, &t); return c; }
 
 // LDS-DMA 3x3x3 kernel (conv_dma.hip): cfg 11 = 256 voxels (4x4x16) x 64 channels, no fused prologue
 #define CONV_CFG_DMA 11
-extern "C" long long gm_conv_dma_lds_bytes(int stride);
-extern "C" int gm_conv_dma_eligible(const GmConvDesc* d);
-extern "C" int gm_conv_dma_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
-extern "C" int gm_conv_dma_variant(int cfg);
 // 14: 4 waves x 64 voxels; 15: stride 2; 16: 512 voxels, 16 waves; 17: sub-pixel up-sampling; 18: 512 voxels, 8 waves x 64 voxels; 19: 512 voxels x 128 channels
 // (21 / 22 / 23: the three tile structures on v_mfma_f32_32x32x16_bf16 of rounds 4-5 -- each verified and measured equal or slower in time, and in round 6
 //  costlier in joules per launch on every C2 shape (profiles/r06_taploop_energy.txt) -- live under experiments/conv_mw, conv_w8, conv_w4; the ids stay retired)
@@ -379,8 +371,6 @@ extern "C" int gm_conv_dma_variant(int cfg);
 // 25: the same kernel over images (3x3 convolutions carried as depth-1 volumes): 16 x 16 pixels x 16 channels per work-group
 #define CONV_CFG_SN 24
 #define CONV_CFG_SN2D 25
-extern "C" int gm_conv_sn_eligible(const GmConvDesc* d);
-extern "C" long long gm_conv_sn_lds_bytes(int cfg);
 static inline bool conv_is_sn(int cfg) { return cfg == CONV_CFG_SN || cfg == CONV_CFG_SN2D; }
 // cfg 25 with stride 2 walks the stride-1 grid (2 n - 1 positions per axis) and stores its even positions (conv_sn.hip)
 static inline long long conv_sn_walk(const GmConvDesc* d, long long n) { return (d->cfg == CONV_CFG_SN2D && d->sh == 2) ? 2 * n - 1 : n; }
@@ -388,17 +378,8 @@ static inline bool conv_is_dma(int cfg) { return cfg == CONV_CFG_DMA || (cfg >= 
 // HBM-bound end convolutions (conv_edge.hip): cfg 12 = C_in <= 4, cfg 13 = C_out == 1; 4x4x16 tiles
 #define CONV_CFG_CIN 12
 #define CONV_CFG_COUT1 13
-extern "C" int gm_conv_cin_eligible(const GmConvDesc* d);
-extern "C" long long gm_conv_cin_lds_bytes(const GmConvDesc* d);
-extern "C" int gm_conv_cin_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
-extern "C" int gm_conv_cout1_eligible(const GmConvDesc* d);
-extern "C" long long gm_conv_cout1_lds_bytes();
-extern "C" int gm_conv_cout1_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
 // cfg 20 = C_out == 1, marching along depth: a work-group walks 2^ltd planes of an 8 x 2^ltw output column (conv_edge.hip)
 #define CONV_CFG_COUT1M 20
-extern "C" int gm_conv_cout1m_eligible(const GmConvDesc* d);
-extern "C" long long gm_conv_cout1m_lds_bytes(const GmConvDesc* d);
-extern "C" int gm_conv_cout1m_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
 static inline bool conv_is_edge(int cfg) { return cfg == CONV_CFG_CIN || cfg == CONV_CFG_COUT1 || cfg == CONV_CFG_COUT1M; }
 
 static bool conv_fast_eligible(const GmConvDesc& d) {

@@ -2,69 +2,13 @@
 #pragma once
 #include "gm_common.h"
 
-// include/gm_amd.h: GmGnTables (the GroupNorm of a token GEMM's input as the statistic tables of its producers, gm_linear_rows_gn)
-struct GmGnTables {
-  const double* stats[2]; int S[2]; int C[2];
-  const float* gamma; const float* beta; float eps; int groups;
-};
-
-struct GmConvDesc {
-  const void* x; long long x_ld;
-  const void* w;                  // packed by gm_pack_conv_weight: [chunk][tap][Cout_pad][BK]
-  const float* bias;              // [Cout] or null
-  const float* pre_scale;         // [N][Cin] or null
-  const float* pre_shift;         // [N][Cin] or null
-  const float* rowvec;            // [B][Cout] fp32 or null, added per (n, cout)
-  long long rowvec_bstride;       // 0 -> broadcast one row over the batch
-  const void* res; long long res_ld;  // residual in output geometry or null
-  void* y; long long y_ld;
-  int N, Cin, Cout;
-  int Ds, Hs, Ws;                 // stored input dims
-  int Do, Ho, Wo;
-  int kd, kh, kw;
-  int sd, sh, sw;
-  int pd, ph, pw;                 // low-side padding (high side is implied by the output size)
-  int dd, dh, dw;                 // dilation
-  int in_mode;                    // 0 direct, 1 nearest up-sample by (fd,fh,fw), 2 zero-insertion by (fd,fh,fw)
-  int fd, fh, fw;
-  int pre_act;                    // 0 none, 1 SiLU, 2 ReLU (applied after the optional affine)
-  int post_act;                   // 0 none, 1 ReLU, 2 tanh, 3 sigmoid, 4 SiLU, 5 LeakyReLU(0.01), 6 GELU (erf)
-  int dtype;
-  int ltd, lth, ltw;              // log2 of the output tile dims
-  int cfg;                        // tile configuration id (see dispatch)
-  int debug_flags;                // 0 in production; bench-only ablation switches of conv_fast.hip
-  double* stats;                  // optional [S][N][Cout][2] (sum, sum of squares) of the OUTPUT, S = gm_conv_stats_slots(desc) = tiles per
-                                  // sample: every work-group STORES its partial exactly once (no atomics, no zero fill); consumers add the S
-                                  // partials in a fixed order, so the statistics -- and everything downstream -- are bit-reproducible run to run
-  // optional fused 1x1 "skip" convolution (ResnetBlock shortcut): y += W_skip * cat(skip_x[0], skip_x[1]) + skip_bias, sources in
-  // the OUTPUT geometry; only the LDS-DMA kernel (cfg 11) implements it
-  const void* skip_x[2]; long long skip_ld[2]; int skip_cin[2];
-  const void* skip_w;             // gm_pack_conv_weight of the [Cout][skip_cin[0] + skip_cin[1]] 1x1 kernel
-  const float* skip_bias;         // [Cout] or null
-  // optional second input source (LDS-DMA kernels only): the input is the channel concatenation cat(x[..., :cin_split], x2) of two
-  // tensors in the same geometry -- torch.cat([h, skip], dim=1) of the decoder blocks, never materialised.  cin_split % BK == 0.
-  const void* x2; long long x2_ld; int cin_split;
-  // optional split-K (LDS-DMA 3x3x3 stride-1 kernels, small grids): the K chunks are dealt to `ksplit` work-groups per tile, each
-  // writing its fp32 partial accumulators to kpartial[ks][n * V + voxel][Cout]; gm_conv_forward then runs the combine kernel (sum of the
-  // slices + bias / timestep row / residual / activation / output statistics).  ksplit <= 1: off.
-  int ksplit; float* kpartial;
-  // optional GroupNorm prologue given as STATISTICS instead of (pre_scale, pre_shift) -- tile configurations 24 / 25 (conv_sn.hip) and the K slices of a split
-  // cfg 11 launch (conv_sk.hip): the consumer folds the per-tile partials of its input (up to two channel-concatenated sources, S_i <= GN_SHORT_MAX_ROWS = 128
-  // rows of [N][C_i][2] fp64 each, as gm_gn_finalize_channels takes them) and
-  // forms scale = rstd * gamma, shift = beta - mean * rstd * gamma itself, in its prologue: bit-identical to gm_gn_finalize_channels, one launch less per norm.
-  // pre_stats[0] == NULL: off (pre_scale / pre_shift as before).  pre_act applies as usual.
-  const double* pre_stats[2]; int pre_S[2]; int pre_C[2];
-  const float* pre_gamma; const float* pre_beta;   // [Cin] fp32 or NULL (1 / 0)
-  float pre_eps; int pre_groups;
-};
-
 // ---- host predicates shared by the eligibility tests of the LDS-DMA kernels ---------------------------------------------------------------------------------
 static inline bool gm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// the statistics form of a GroupNorm prologue (GmConvDesc.pre_stats / GmGnTables): one or two 16-byte aligned sources of 1 .. GN_SHORT_MAX_ROWS rows whose
+// the statistics form of a GroupNorm prologue (GmConvDesc.pre_stats / GmGnTables): one or two 16-byte aligned sources of 1 .. GM_GN_SHORT_MAX_ROWS rows whose
 // channels add up to cin; no second source, no second channel count.  (Each consumer adds the bounds of its own LDS tables.)
 static inline bool gm_gn_stats_form_ok(const double* const stats[2], const int S[2], const int C[2], int cin) {
-  return stats[0] != nullptr && S[0] >= 1 && S[0] <= GN_SHORT_MAX_ROWS && C[0] > 0 &&
-         ((stats[1] == nullptr && C[1] == 0 && C[0] == cin) || (stats[1] != nullptr && S[1] >= 1 && S[1] <= GN_SHORT_MAX_ROWS && C[1] > 0 && C[0] + C[1] == cin)) &&
+  return stats[0] != nullptr && S[0] >= 1 && S[0] <= GM_GN_SHORT_MAX_ROWS && C[0] > 0 &&
+         ((stats[1] == nullptr && C[1] == 0 && C[0] == cin) || (stats[1] != nullptr && S[1] >= 1 && S[1] <= GM_GN_SHORT_MAX_ROWS && C[1] > 0 && C[0] + C[1] == cin)) &&
          gm_aligned16(stats[0]) && gm_aligned16(stats[1]);
 }
 // the second input source of a virtual channel concatenation: same geometry, chunk-aligned split inside C_in, vector-aligned pitch and base

@@ -1000,11 +1000,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void conv_dma_kernel(const GmConvDes
 // four 128-row weight panels, padded to the 36 KiB of the epilogue's transpose scratch); 5 = 8x4x16 tile x 128 output channels (three 384-row
 // weight panels).  Every variant ends with the 512-byte epilogue addend vector.
 // tile configuration 24 (conv_sn.hip: small volumes, K-complete on 16-channel output blocks) shares this file's entry points
-extern "C" int gm_conv_sn_eligible(const GmConvDesc* d);
-extern "C" int gm_conv_sn_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
 // the K slices of a split-K launch (cfg 11 geometry) run on conv_sk.hip's kernel: one work-group per CU, patch + all nine panels of a chunk resident
-extern "C" int gm_conv_sk_eligible(const GmConvDesc* d);
-extern "C" int gm_conv_sk_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
 
 #if DMA_PART(0)
 extern "C" long long gm_conv_dma_lds_bytes(int variant) {
@@ -1040,8 +1036,6 @@ extern int gm_dma_grid_cap, gm_dma_phase_skew;
 #endif
 #define g_dma_grid_cap gm_dma_grid_cap
 #define g_dma_phase_skew gm_dma_phase_skew
-extern "C" long long gm_conv_dma_lds_bytes(int variant);
-extern "C" int gm_conv_dma_variant(int cfg);
 static int dma_device_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -1144,11 +1138,6 @@ static void launch_dma(const GmConvDesc& d, unsigned nblocks, hipStream_t st) {
     if (d.dtype == GM_BF16) { using T = bf16_raw; __VA_ARGS__; return 0; }                   \
     return -2;                                                                               \
   } while (0)
-extern "C" int gm_conv_dma_launch_part0(const GmConvDesc* dp, unsigned nblocks, void* stream);
-extern "C" int gm_conv_dma_launch_part1(const GmConvDesc* dp, unsigned nblocks, void* stream);
-extern "C" int gm_conv_dma_launch_part2(const GmConvDesc* dp, unsigned nblocks, void* stream);
-extern "C" int gm_conv_dma_launch_part3(const GmConvDesc* dp, unsigned nblocks, void* stream);
-extern "C" int gm_conv_dma_launch_part4(const GmConvDesc* dp, unsigned nblocks, void* stream);
 #if DMA_PART(0)
 extern "C" int gm_conv_dma_launch_part0(const GmConvDesc* dp, unsigned nblocks, void* stream) {  // cfg 11: 8 waves x 32 voxels, two work-groups per CU
   const GmConvDesc& d = *dp; hipStream_t st = (hipStream_t)stream;

@@ -29,8 +29,9 @@ template <int ND> struct Geom {
   static constexpr int PH = ND == 3 ? 6 : 18, PLANE = ND == 3 ? 112 : 336, PROWS = (ND == 3 ? 6 : 1) * PLANE, PPIECES = PROWS / 16;
   static constexpr int PATCH_BYTES = PROWS * DMA_ROWB, W_BYTES = NTAP * BN * DMA_ROWB;  // 43 008 + 27 648 (3-D), 21 504 + 9 216 (2-D)
   static constexpr int AFF_OFF = PATCH_BYTES + W_BYTES, AFF_WAVE = PATCH_AFF_WAVE;  // per wave: [scale | shift] of the chunk being staged (PRE, scale / shift arrays given)
-  static constexpr int MAX_CIN_TAB = 384;                                // ... or ONE table [scale[Cin] | shift[Cin]] built from the input's statistics (PRE, pre_stats),
-  static constexpr int AFF_BYTES = 2 * MAX_CIN_TAB * 4 + MAX_CIN_TAB * 16;  //     behind it the per-channel fp64 (sum, sum of squares) the table is built from: 9 KiB
+  // ... or ONE table [scale[Cin] | shift[Cin]] built from the input's statistics (PRE, pre_stats) over up to GM_GN_TABLE_MAX_CHANNELS (384) channels,
+  //     behind it the per-channel fp64 (sum, sum of squares) the table is built from: 9 KiB
+  static constexpr int AFF_BYTES = 2 * GM_GN_TABLE_MAX_CHANNELS * 4 + GM_GN_TABLE_MAX_CHANNELS * 16;
   static constexpr int STAT_OFF = AFF_OFF + AFF_BYTES;                   // [wave][16 channels][sum, sum of squares] fp32
   static constexpr int LDS_BYTES = STAT_OFF + MAXW * BN * 8;             // 80 896 (3-D): two work-groups per CU; 40 960 (2-D)
   static_assert(AFF_BYTES >= MAXW * AFF_WAVE, "the per-wave scale / shift copies fit too");
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void conv_sn_kernel(const
   // ---- PRE from statistics: the table [scale[Cin] | shift[Cin]] over every input channel, behind it the [Cin] fp64 channel sums it is built from -- under the
   // flight of the first requests (its closing barrier: the prologue of chunk 0 runs in front of the first tap-loop barrier) ------------------------------------
   if (PRE && from_stats)
-    gn_short_table<64 * NW>(reinterpret_cast<float*>(smem + AFF_OFF), p.Cin, reinterpret_cast<double*>(smem + AFF_OFF + 2 * GE::MAX_CIN_TAB * 4), 0, p.Cin, 0, p.Cin,
+    gn_short_table<64 * NW>(reinterpret_cast<float*>(smem + AFF_OFF), p.Cin, reinterpret_cast<double*>(smem + AFF_OFF + 2 * GM_GN_TABLE_MAX_CHANNELS * 4), 0, p.Cin, 0, p.Cin,
                             p.Cin / p.pre_groups, p.pre_stats[0], p.pre_S[0], p.pre_C[0], p.pre_stats[1], p.pre_S[1], p.pre_C[1], p.N, n,
                             (long long)p.Ds * p.Hs * p.Ws, p.pre_eps, p.pre_gamma, p.pre_beta, tid);
 
@@ -343,7 +344,7 @@ extern "C" int gm_conv_sn_eligible(const GmConvDesc* d) {
            (reinterpret_cast<uintptr_t>(d->pre_shift) & 15) == 0 && (d->Cin % 4) == 0) ||
           // the statistics form: short tables (their rows all sit in one wave of the fold), whole groups, the table over all input channels in LDS
           (d->pre_scale == nullptr && d->pre_shift == nullptr && gm_gn_stats_form_ok(d->pre_stats, d->pre_S, d->pre_C, d->Cin) && d->pre_groups > 0 &&
-           d->Cin % d->pre_groups == 0 && d->Cin <= sn::Geom<3>::MAX_CIN_TAB && d->in_mode == 0)) &&
+           d->Cin % d->pre_groups == 0 && d->Cin <= GM_GN_TABLE_MAX_CHANNELS && d->in_mode == 0)) &&
          gm_conv_second_source_ok(d, bk, vecw) && gm_conv_shortcut_ok(d, bk, vecw) &&
          // (any C_out / row pitch / alignment of y, res, bias, rowvec: four channels per lane go out as one vector where all of them allow it, element-wise otherwise)
          (long long)d->N * d->Ds * d->Hs * d->Ws < (1LL << 31) && (long long)d->N * d->Do * d->Ho * d->Wo < (1LL << 31);

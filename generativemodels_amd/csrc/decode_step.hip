@@ -12,60 +12,6 @@
 #include "attn_common.h"
 #include "conv_common.h"
 
-extern "C" int gm_embed_tokens_dev(const long long* indices, const void* token_weight, const void* position_weight, void* out, long long batch,
-                                   int seq_len, int C, int pos0, int num_tokens, int max_positions, int dtype, const int* pos_dev, void* stream);
-extern "C" int gm_attention_decode_dev(const GmAttnDesc* dp, const int* lk_dev, void* stream);
-extern "C" int gm_attention_decode_split(const GmAttnDesc* dp, const int* lk_dev, float* ws, int nsplit, int merge, int cap, void* stream);
-extern "C" int gm_mlp_rows_fusable(int rows, int C, int M, int dtype);
-extern "C" int gm_mlp_rows(const void* x, const float* ln_g, const float* ln_b, float ln_eps, const void* w1, const float* b1, const void* w2,
-                           float* P, int rows, int C, int M, int act, int dtype, void* stream);
-extern "C" int gm_linear_rows_mlpmerge(const float* P, int nj, const void* x1, const float* b2, void* x0_out, const float* ln_g, const float* ln_b,
-                                       float ln_eps, const void* w, const float* bias, void* y, long long y_ld, void* y1, void* y2, long long y12_ld,
-                                       int split, int rows, int cin, int cout, int post_act, int dtype, const int* off_dev, long long off_mul,
-                                       void* stream);
-struct QkvAttnArgs {  // small_ops.hip
-  const void* x0;
-  const float* mlp_p; int mlp_nj; const void* mlp_x1; const float* mlp_b2; void* x0_out;
-  const float* ln_g; const float* ln_b; float ln_eps;
-  const void* w; const float* bias;
-  void* kcache; void* vcache;
-  int B, H, C, dh, cap, pos; const int* pos_dev;
-  float scale; float* ws; int chunk, sc_elems;
-};
-extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream);
-extern "C" int gm_qkv_attn_rows_plan(const QkvAttnArgs* ap, int dtype, int* ng, int* um);  // which instantiation would take it; launches nothing
-extern "C" int gm_linear_rows_takes_ksplit(int rows, int cin, int dtype);
-extern "C" int gm_linear_rows_kvmerge(const float* kv_ws, int kv_ns, int kv_dh, const void* w, const float* bias, const void* res, long long res_ld,
-                                      void* y, long long y_ld, int rows, int cin, int cout, int dtype, void* stream);
-extern "C" int gm_layernorm(const void* x, long long x_ld, void* y, long long y_ld, const float* gamma, const float* beta, long long rows,
-                            int C, float eps, int dtype, void* stream);
-extern "C" int gm_copy_channels(const void* src, long long src_ld, int src_dtype, void* dst, long long dst_ld, int dst_dtype,
-                                long long rows, int C, void* stream);
-extern "C" int gm_attention_forward(const GmAttnDesc* dp, void* stream);
-
-struct GmDecodeBlock {
-  const float *ln1_g, *ln1_b;
-  const void* w_qkv; const float* b_qkv;  // packed [3C][C] (gm_pack_conv_weight), bias or null
-  const void* w_o; const float* b_o;
-  const float *ln3_g, *ln3_b;
-  const void* w_1; const float* b_1;      // C -> M
-  const void* w_2; const float* b_2;      // M -> C
-  void* k_cache; void* v_cache;           // [B][max_len][C]
-};
-
-struct GmDecodeDesc {
-  int B, C, M, heads, depth, max_len, num_tokens, dtype;
-  float ln_eps;
-  int pos;                                // position of the token being fed (its K/V land in cache row `pos`)
-  const long long* tokens;                // [B] token ids on the device
-  const void* tok_emb; const void* pos_emb;
-  const GmDecodeBlock* blocks;            // host array of `depth` entries
-  const void* w_logits; const float* b_logits;
-  void* logits;                           // [B][num_tokens] in dtype
-  void* scratch; long long scratch_bytes; // gm_decode_scratch_bytes(B, C, M, dtype)
-  const int* pos_dev;                     // optional: the position is read from device memory at run time (HIP-graph replay); `pos` is ignored
-};
-
 static long long elt(int dtype) { return dtype == GM_F32 ? 4 : 2; }
 // Context windows longer than DECODE_SPLIT_MIN_LEN keys run the single-query attention split over DECODE_KV_SPLITS key ranges (small_ops.hip).
 // The choice depends on the window (max_len), not on the position, so a step issued with a host position and its graph replay agree bit for bit.
@@ -80,28 +26,11 @@ extern "C" long long gm_decode_scratch_bytes(int B, int C, int M, int dtype) {
          r((long long)B * DECODE_KV_SPLITS * 3 * C * 4) + r((long long)((M + 63) / 64) * B * C * 4);  // + the MLP's K-slice partials
 }
 
-extern "C" int gm_linear_rows(const void* x, long long x_ld, const void* w, const float* bias, const void* res, long long res_ld, void* y,
-                              long long y_ld, int rows, int cin, int cout, int pre_act, int post_act, int dtype, void* stream);
-
-extern "C" int gm_linear_rows_ln(const void* x, long long x_ld, const float* ln_g, const float* ln_b, float ln_eps, const void* w,
-                                 const float* bias, void* y, long long y_ld, void* y1, void* y2, long long y12_ld, int split, int rows, int cin,
-                                 int cout, int post_act, int dtype, const int* off_dev, long long off_mul, void* stream);
-
 // y[rows][cout] = act(x[rows][cin] W^T + b) (+ res) through the small-row GEMM kernel (small_ops.hip)
 static int linear_rows(const void* x, long long x_ld, const void* w, const float* b, const void* res, long long res_ld, void* y, long long y_ld,
                        int rows, int cin, int cout, int post_act, int dtype, void* stream) {
   return gm_linear_rows(x, x_ld, w, b, res, res_ld, y, y_ld, rows, cin, cout, 0, post_act, dtype, stream);
 }
-
-// (include/gm_amd.h: the GM_DECODE_PLAN_* indices and values; tests/test_decode_routes.py pins the plans through the header's names)
-enum {
-  GM_DECODE_PLAN_SPLIT_KV, GM_DECODE_PLAN_QKV_NG, GM_DECODE_PLAN_QKV_UM, GM_DECODE_PLAN_QKV_INPUT, GM_DECODE_PLAN_OUT_MERGE, GM_DECODE_PLAN_ATTN_ENTRY,
-  GM_DECODE_PLAN_MLP_FUSED, GM_DECODE_PLAN_KSPLIT_QKV, GM_DECODE_PLAN_KSPLIT_OUT, GM_DECODE_PLAN_KSPLIT_MLP_UP, GM_DECODE_PLAN_KSPLIT_MLP_DOWN,
-  GM_DECODE_PLAN_KSPLIT_LOGITS, GM_DECODE_PLAN_COUNT
-};
-enum { GM_DECODE_INPUT_ROW, GM_DECODE_INPUT_MLP_MERGE };
-enum { GM_DECODE_MERGE_NONE, GM_DECODE_MERGE_OUT_PROJ, GM_DECODE_MERGE_COMBINE };
-enum { GM_DECODE_ENTRY_NONE, GM_DECODE_ENTRY_HOST_POS, GM_DECODE_ENTRY_DEVICE_POS };
 
 // ---- the route plan ---------------------------------------------------------------------------------------------------------------------
 // Every route decision of the step, taken in ONE place: block `blk`'s routes (and the step-wide ones) as GM_DECODE_PLAN_COUNT ints, indexed

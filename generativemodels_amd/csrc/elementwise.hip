@@ -14,21 +14,6 @@
 // reference and passed by value; the kernel mirrors the reference's op order *without* fma contraction so that an fp32
 // step is bit-identical to the reference CPU result.  bf16 tensors are computed in fp32 and rounded once.
 // ---------------------------------------------------------------------------------------------------------------------
-struct GmStepParams {
-  int mode;       // 0 = DDIM, 1 = DDPM, 2 = PNDM transfer (formula (9): k0*x - (k1*e)/c_prev, e = model output or its v-prediction transform)
-  int pred_type;  // 0 epsilon, 1 sample, 2 v_prediction
-  float c_sa;     // alpha_prod_t ** 0.5
-  float c_sb;     // beta_prod_t ** 0.5
-  int clip;
-  float clip_lo, clip_hi;
-  float c_prev;   // DDIM: alpha_prod_t_prev ** 0.5
-  float c_dir;    // DDIM: (1 - alpha_prod_t_prev - std_dev_t**2) ** 0.5
-  float k0, k1;   // DDPM: pred_original_sample_coeff, current_sample_coeff
-  int noise_mode; // 0 none, 1 c_noise * noise, 2 learned: sqrt(pv) * noise, 3 learned_range
-  float c_noise;  // DDIM: variance**0.5 * eta ; DDPM fixed_*: variance ** 0.5
-  float min_log, max_log;  // learned_range
-};
-
 // BITS: the Gaussian noise of a bf16 chain comes as the CPU generator's byte draws + the pair table of host_noise.py (gm_normal_bf16_from_bits' lookup, here in the
 // step's own kernel: element i of block b = i / 16 is the cos branch (i % 16 < 8) or the sin branch of the byte pair (bits[16 b + i % 8], bits[16 b + 8 + i % 8]))
 template <typename T, bool BITS>
@@ -221,18 +206,6 @@ extern "C" int gm_lincomb(const void* const* x, const float* c, int k, float pos
 // accumulated into total[n].  All scalar sub-expressions are evaluated on the host as the reference evaluates them (0-dim
 // fp32 torch-CPU tensors) and passed by value.
 // ---------------------------------------------------------------------------------------------------------------------
-struct GmKlParams {
-  int pred_type;      // 0 epsilon, 1 sample, 2 v_prediction
-  float c_sa, c_sb;   // alpha_prod_t ** 0.5, beta_prod_t ** 0.5
-  int clip;           // clamp predicted x0 to [-1, 1] (inferer.py:222-223)
-  float k0, k1;       // predicted mean = k0 * pred_x0 + k1 * x_t
-  float m0, m1;       // posterior mean = m0 * x_0 + m1 * x_t        (ddpm.py:151-154)
-  int t0;             // 1: decoder NLL, 0: KL between normals
-  float s;            // KL: (-1 + log_pred_var - log_post_var) + exp(log_post_var - log_pred_var)
-  float e;            // KL: exp(-log_pred_var);   NLL: inv_stdv = exp(-log_scales)
-  float half_bin;     // NLL: bin_width / 2
-};
-
 __device__ __forceinline__ float approx_std_normal_cdf(float x, float c) {
   const float x3 = __fmul_rn(__fmul_rn(x, x), x);  // torch.pow(x, 3) is x*x*x
   return __fmul_rn(0.5f, __fadd_rn(1.0f, tanhf(__fmul_rn(c, __fadd_rn(x, __fmul_rn(0.044715f, x3))))));

@@ -3,16 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define GM_F32 0
-#define GM_BF16 1
+#include "gm_amd.h"       // the public interface (include/): every Gm* struct, GM_* constant and exported prototype, defined there only
+#include "gm_internal.h"  // the cross-file helpers that are not part of it
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef uint16_t bf16_raw;  // storage type of a bf16 element in HBM / LDS
 
-// ---- error plumbing shared by every extern "C" entry point ---------------------------------------------------------
-extern "C" void gm_set_error(const char* where, int code, const char* msg);
+// ---- error plumbing shared by every extern "C" entry point (gm_set_error: capi.cpp) --------------------------------
 #define GM_FAIL(code, msg)                 \
   do {                                     \
     gm_set_error(__func__, (code), (msg)); \
@@ -70,10 +68,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// ---- GroupNorm finalisation over SHORT statistic tables (every source S <= GN_SHORT_MAX_ROWS rows of [N][C_i][2] fp64 partials) -- shared by gm_gn_finalize_channels
+// ---- GroupNorm finalisation over SHORT statistic tables (every source S <= GM_GN_SHORT_MAX_ROWS rows of [N][C_i][2] fp64 partials) -- shared by gm_gn_finalize_channels
 // (groupnorm.hip) and the consumer-side prologues (gn_short_table below), which must agree bit for bit: a channel's partials are added in ROW order, a group is the sum
 // of its channels in CHANNEL order, everything in fp64.  Channel c of the concatenation (C0 + C1 channels) lives in source 0 when c < C0.
-#define GN_SHORT_MAX_ROWS 128  // (64 until the second half of round 6: the 32^3 level of a latent UNet leaves 128-row tables -- one partial per 256-voxel tile)
+// (the bound was 64 until the second half of round 6: the 32^3 level of a latent UNet leaves 128-row tables -- one partial per 256-voxel tile)
 __device__ __forceinline__ double2 gn_short_channel_sum(const double* s0, int S0, int C0, const double* s1, int S1, int C1, int N, int n, int c) {
   const bool first = c < C0;
   const double* src = first ? s0 + ((long long)n * C0 + c) * 2 : s1 + ((long long)n * C1 + (c - C0)) * 2;

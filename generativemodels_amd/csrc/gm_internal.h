@@ -1,0 +1,85 @@
+// Cross-file helpers of libgmamd.so that are NOT part of the public interface (include/gm_amd.h), each declared once, grouped by the file that defines
+// them.  gm_common.h includes this header, so the defining file sees its own declaration and the compiler holds definition, declaration and every caller to
+// one signature: these are extern "C" (no mangling), and a disagreement would otherwise link cleanly.  A helper gm_amd.h declares gets no line here.
+#pragma once
+#include "gm_amd.h"
+
+extern "C" {
+
+// ---- capi.cpp
+void gm_set_error(const char* where, int code, const char* msg);
+
+// ---- conv_fast.hip: the stride-1 register-staged kernels (cfg 5 .. 10; variant = cfg - 4)
+long long gm_conv_fast_lds_bytes(const GmConvDesc* d, int bn);
+long long gm_conv_fast_max_patch(int variant);
+int gm_conv_fast_variant_geometry(int variant, int* voxels, int* channels, int* threads);
+int gm_conv_fast_launch(const GmConvDesc* dp, int variant, unsigned nblocks, void* stream);
+
+// ---- conv_dma.hip: the LDS-DMA kernels (cfg 11, 14 .. 19); launch_part<k> = the instantiations of the translation unit built with GM_DMA_PART = k
+long long gm_conv_dma_lds_bytes(int variant);
+int gm_conv_dma_variant(int cfg);
+int gm_conv_dma_eligible(const GmConvDesc* d);
+int gm_conv_dma_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_dma_launch_part0(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_dma_launch_part1(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_dma_launch_part2(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_dma_launch_part3(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_dma_launch_part4(const GmConvDesc* dp, unsigned nblocks, void* stream);
+
+// ---- conv_sk.hip: the K slices of a split cfg 11 launch
+int gm_conv_sk_eligible(const GmConvDesc* d);
+int gm_conv_sk_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
+
+// ---- conv_sn.hip: small volumes and images, K-complete (cfg 24 / 25)
+int gm_conv_sn_eligible(const GmConvDesc* d);
+long long gm_conv_sn_lds_bytes(int cfg);
+int gm_conv_sn_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
+
+// ---- conv_edge.hip: the HBM-bound end convolutions (cfg 12: C_in <= 4; cfg 13 / 20: C_out == 1)
+int gm_conv_cin_eligible(const GmConvDesc* d);
+long long gm_conv_cin_lds_bytes(const GmConvDesc* d);
+int gm_conv_cin_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_cout1_eligible(const GmConvDesc* d);
+long long gm_conv_cout1_lds_bytes(void);
+int gm_conv_cout1_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
+int gm_conv_cout1m_eligible(const GmConvDesc* d);
+long long gm_conv_cout1m_lds_bytes(const GmConvDesc* d);
+int gm_conv_cout1m_launch(const GmConvDesc* dp, unsigned nblocks, void* stream);
+
+// ---- attention_dma.hip: 0 = the LDS-DMA kernel took the launch
+int gm_attention_dma_try(const GmAttnDesc* dp, void* stream);
+
+// ---- transformer_ops.hip: gm_embed_tokens with the position read from device memory (pos_dev != NULL)
+int gm_embed_tokens_dev(const long long* indices, const void* token_weight, const void* position_weight, void* out, long long batch, int seq_len, int C,
+                        int pos0, int num_tokens, int max_positions, int dtype, const int* pos_dev, void* stream);
+
+// ---- small_ops.hip: the kernels of the decode step (decode_step.hip) -- single-query attention, row GEMMs with fused prologues, the fused MLP
+int gm_attention_decode_try(const GmAttnDesc* dp, void* stream);
+int gm_attention_decode_dev(const GmAttnDesc* dp, const int* lk_dev, void* stream);
+int gm_attention_decode_split(const GmAttnDesc* dp, const int* lk_dev, float* ws, int nsplit, int merge, int cap, void* stream);
+int gm_linear_rows_takes_ksplit(int rows, int cin, int dtype);
+int gm_linear_rows_ln(const void* x, long long x_ld, const float* ln_g, const float* ln_b, float ln_eps, const void* w, const float* bias, void* y,
+                      long long y_ld, void* y1, void* y2, long long y12_ld, int split, int rows, int cin, int cout, int post_act, int dtype,
+                      const int* off_dev, long long off_mul, void* stream);
+int gm_linear_rows_kvmerge(const float* kv_ws, int kv_ns, int kv_dh, const void* w, const float* bias, const void* res, long long res_ld, void* y,
+                           long long y_ld, int rows, int cin, int cout, int dtype, void* stream);
+int gm_linear_rows_mlpmerge(const float* P, int nj, const void* x1, const float* b2, void* x0_out, const float* ln_g, const float* ln_b, float ln_eps,
+                            const void* w, const float* bias, void* y, long long y_ld, void* y1, void* y2, long long y12_ld, int split, int rows, int cin,
+                            int cout, int post_act, int dtype, const int* off_dev, long long off_mul, void* stream);
+int gm_mlp_rows_fusable(int rows, int C, int M, int dtype);
+int gm_mlp_rows(const void* x, const float* ln_g, const float* ln_b, float ln_eps, const void* w1, const float* b1, const void* w2, float* P, int rows,
+                int C, int M, int act, int dtype, void* stream);
+// LayerNorm + q | k | v + one key range of the single-query attention in one launch (qkv_attn_rows_kernel, which takes the struct by value)
+struct QkvAttnArgs {
+  const void* x0;                                                       // [B][C] rows, or null with the partial source below
+  const float* mlp_p; int mlp_nj; const void* mlp_x1; const float* mlp_b2; void* x0_out;
+  const float* ln_g; const float* ln_b; float ln_eps;
+  const void* w; const float* bias;                                     // packed [chunk][3C pad 16][BK]; fp32 [3C] or null
+  void* kcache; void* vcache;                                           // [B][cap][C]
+  int B, H, C, dh, cap, pos; const int* pos_dev;
+  float scale; float* ws; int chunk, sc_elems;
+};
+int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream);
+int gm_qkv_attn_rows_plan(const QkvAttnArgs* ap, int dtype, int* ng, int* um);  // which instantiation would take it; launches nothing
+
+}  // extern "C"

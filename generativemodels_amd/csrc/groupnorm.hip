@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void gn_finalize_channels_kernel(const double*
   }
 }
 
-// SHORT tables (every source S <= GN_SHORT_MAX_ROWS): a thread owns a channel of the group and adds its rows in row order; thread 0 adds the channels in channel order -- the
+// SHORT tables (every source S <= GM_GN_SHORT_MAX_ROWS): a thread owns a channel of the group and adds its rows in row order; thread 0 adds the channels in channel order -- the
 // order conv_sn.hip's consumer-side prologue reproduces (gm_common.h: gn_short_*), so that a norm finalised there and one finalised here agree bit for bit.
 __global__ __launch_bounds__(256) void gn_finalize_channels_short_kernel(const double* __restrict__ s0, int S0, int C0, const double* __restrict__ s1, int S1, int C1,
                                                                         int N, int G, long long V, float eps, const float* __restrict__ gamma,
@@ -399,7 +399,7 @@ extern "C" int gm_gn_finalize_channels(const double* stats0, int S0, int C0, con
   // the short kernel's LDS: the group's [cpg + 1] pairs and, staged, its rows -- both within the 64 KiB a launch gets unasked (cpg = 4096 asked for 65 552
   // bytes, cpg = 2048 with one staged row likewise: wider groups go to the long-table kernel, rows that do not fit are walked unstaged)
   const size_t sums = (size_t)(2 * cpg + 2) * sizeof(double), lds_max = 64 * 1024;
-  if (S0 <= GN_SHORT_MAX_ROWS && (C1 == 0 || S1 <= GN_SHORT_MAX_ROWS) && sums <= lds_max) {  // short tables: the order the consumer-side finalisation shares (ops.GnRecipe)
+  if (S0 <= GM_GN_SHORT_MAX_ROWS && (C1 == 0 || S1 <= GM_GN_SHORT_MAX_ROWS) && sums <= lds_max) {  // short tables: the order the consumer-side finalisation shares (ops.GnRecipe)
     const int smax = C1 && S1 > S0 ? S1 : S0;
     const size_t staged = (size_t)smax * cpg * 2 * sizeof(double);
     const int staged_rows = staged <= 48 * 1024 && sums + staged <= lds_max ? smax : 0;  // (else: a thread walks its channel's rows itself -- the same sums)

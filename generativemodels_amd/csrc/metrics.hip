@@ -5,7 +5,6 @@
 // Every reduction is per work-group partials + a fold in a fixed order: no atomics, results are bit-reproducible.
 #include "gm_common.h"
 
-#define GM_F16 2             // metrics only: inputs are upcast in registers, nothing is stored in fp16
 #define SSIM_MAX_WINDOW 16   // taps per axis the kernel is built for
 #define SSIM_TH 16           // output tile (H, W) of a work-group; 256 threads, one output column each
 #define SSIM_TW 16

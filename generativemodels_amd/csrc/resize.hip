@@ -10,14 +10,6 @@
 // a voxel's channels then share one lane and one walk over the tables).  fp32 accumulation, one rounding on store.  No LDS.
 #include "gm_common.h"
 
-struct GmResizeDesc {
-  int n_in[3];             // D, H, W of x (a missing leading axis: 1, with the identity table)
-  int n_out[3];            // D, H, W of y
-  const int* start[3];     // [n_out[a] + 1]
-  const int* index[3];     // [start[a][n_out[a]]], every entry in [0, n_in[a])
-  const float* weight[3];  // [start[a][n_out[a]]]
-};
-
 static int resize_grid(long long total, int per_block = 256) {
   long long g = (total + per_block - 1) / per_block;
   if (g > 256 * 16) g = 256 * 16;

@@ -765,7 +765,7 @@ extern "C" int gm_linear_rows_affine_vt(const void* x, long long x_ld, const flo
 extern "C" int gm_linear_rows_gn(const void* x, long long x_ld, const GmGnTables* gn, int n_samples, int rows_per_sample, const void* w, const float* bias,
                                  const void* res, long long res_ld, void* y, long long y_ld, int rows, int cin, int cout, int pre_act, int post_act, void* vt,
                                  int vt_c0, int vt_dh, int dtype, void* stream) {
-  GM_REQUIRE(gn && gn->stats[0] && gn->groups > 0 && cin % gn->groups == 0 && cin <= 384, "GroupNorm tables: whole groups, at most 384 channels");
+  GM_REQUIRE(gn && gn->stats[0] && gn->groups > 0 && cin % gn->groups == 0 && cin <= GM_GN_TABLE_MAX_CHANNELS, "GroupNorm tables: whole groups, at most 384 channels");
   const int gn_C[2] = {gn->C[0], gn->stats[1] ? gn->C[1] : 0};  // (C[1] is not read without a second source)
   GM_REQUIRE(gm_gn_stats_form_ok(gn->stats, gn->S, gn_C, cin), "short, 16-byte aligned statistic tables covering the input channels");
   GM_REQUIRE(n_samples > 0 && rows_per_sample > 0 && rows_per_sample % 64 == 0 && rows == n_samples * rows_per_sample, "whole 64-row groups per sample");
@@ -1097,16 +1097,6 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(GmAttnDesc p, co
 // weight fragments at entry; what the fusion buys is one ~4.5 us launch per block of the token's dependent chain.
 // NG = 3 * dh / 16 output groups, UM = K chunks per wave (host: C % BK == 0, ceil(C / BK / 4) <= UM).
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct QkvAttnArgs {
-  const void* x0;                                                       // [B][C] rows, or null with the partial source below
-  const float* mlp_p; int mlp_nj; const void* mlp_x1; const float* mlp_b2; void* x0_out;
-  const float* ln_g; const float* ln_b; float ln_eps;
-  const void* w; const float* bias;                                     // packed [chunk][3C pad 16][BK]; fp32 [3C] or null
-  void* kcache; void* vcache;                                           // [B][cap][C]
-  int B, H, C, dh, cap, pos; const int* pos_dev;
-  float scale; float* ws; int chunk, sc_elems;
-};
-
 template <typename T, int NG, int UM>
 __global__ __launch_bounds__(256) void qkv_attn_rows_kernel(QkvAttnArgs a) {
   constexpr int BK = ConvTraits<T>::BK, VECW = ConvTraits<T>::VECW, NS = GM_DECODE_KV_SPLITS;

@@ -13,7 +13,6 @@
 // Reductions are per work-group fp64 partials folded in a fixed order: no atomics, bit-reproducible.
 #include "gm_common.h"
 
-#define GM_F16 2
 #define DFT_COMPLEX 3       // complex fp32 lines
 #define DFT_HERMITIAN 4     // source only: a line holds the n / 2 + 1 bins of a Hermitian spectrum, expanded to n on load
 #define DFT_THREADS 256
@@ -23,27 +22,7 @@
 #define DFT_LINE_TABLE_BYTES 1024  // DFT_MAX_LINES x (source, destination) offsets
 #define DFT_MAX_STAGES 16
 #define DFT_MAX_LENGTH ((DFT_LDS_BYTES - DFT_LINE_TABLE_BYTES) / 16 - 1)
-
-struct GmDftDesc {
-  const void* src;
-  void* dst;
-  const float* twiddle;     // [n][2]: exp(-2 pi i j / n)
-  const float* scale_dev;   // NULL, or one device fp32 multiplied into `scale`
-  long long src_stride[4];  // the grid of lines, last axis fastest; elements of the respective kind
-  long long dst_stride[4];
-  int extent[4];
-  long long src_axis_stride;
-  long long dst_axis_stride;
-  int n;                    // transform length
-  int n_valid;              // points read from a line (the rest is zero); n for DFT_HERMITIAN
-  int n_store;              // points stored, from 0
-  int src_kind;             // GM_F32 / GM_BF16 / GM_F16 real, DFT_COMPLEX, DFT_HERMITIAN
-  int dst_kind;             // GM_F32 / GM_BF16 / GM_F16: the real part; DFT_COMPLEX
-  int inverse;              // conjugate twiddles
-  float scale;
-  int nstages;
-  int radix[DFT_MAX_STAGES];
-};
+static_assert(sizeof(GmDftDesc::radix) == DFT_MAX_STAGES * sizeof(int), "GmDftDesc.radix (include/gm_amd.h) holds DFT_MAX_STAGES radices");
 
 __device__ __forceinline__ float2 c_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 c_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }

@@ -23,9 +23,6 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const long long* __re
   }
 }
 
-extern "C" int gm_embed_tokens_dev(const long long* indices, const void* token_weight, const void* position_weight, void* out, long long batch,
-                                   int seq_len, int C, int pos0, int num_tokens, int max_positions, int dtype, const int* pos_dev, void* stream);
-
 extern "C" int gm_embed_tokens(const long long* indices, const void* token_weight, const void* position_weight, void* out,
                                long long batch, int seq_len, int C, int pos0, int num_tokens, int max_positions, int dtype, void* stream) {
   return gm_embed_tokens_dev(indices, token_weight, position_weight, out, batch, seq_len, C, pos0, num_tokens, max_positions, dtype, nullptr, stream);

@@ -786,8 +786,9 @@ def _fresh_channel_stats(x: torch.Tensor) -> torch.Tensor:
 GN_IN_CONSUMER = os.environ.get("GM_GN_IN_CONSUMER", "1") != "0"  # short statistic tables: the fold + finalisation in the consumer convolution's prologue (cfg 24 / 25)
 GN_IN_TOKEN_GEMM = True  # ... and in the wide token GEMM (the q | k | v projection of an attention block)
 GN_IN_SPLIT_SLICES = True  # ... also in the K slices of a split launch (conv_sk.hip, second half of round 6)
-GN_IN_CONSUMER_MAX_ROWS = 128  # = GN_SHORT_MAX_ROWS of csrc/gm_common.h (64 until the 32^3 level's 128-row tables were measured)
-GN_IN_CONSUMER_MAX_CHANNELS = 384  # = sn::Geom::MAX_CIN_TAB of csrc/conv_sn.hip: the (scale | shift) table a consumer builds in LDS covers that many input channels
+# the two limits of include/gm_amd.h (tests/test_abi.py holds them to the header's values)
+GN_IN_CONSUMER_MAX_ROWS = 128  # = GM_GN_SHORT_MAX_ROWS (64 until the 32^3 level's 128-row tables were measured)
+GN_IN_CONSUMER_MAX_CHANNELS = 384  # = GM_GN_TABLE_MAX_CHANNELS: the (scale | shift) table a consumer builds in LDS covers that many input channels
 
 
 class GnRecipe:
@@ -1288,7 +1289,7 @@ def _token_gemm_takes_recipe(g: ConvGeometry, f: ConvFacts) -> bool:
     if not (GN_IN_TOKEN_GEMM and f.pre == "recipe" and not g.transposed):
         return False
     rn, cs, groups, table_rows = f.recipe
-    return (rn == g.n and sum(cs) == g.cin and g.cin <= 384 and g.cin % (64 // g.es) == 0 and g.cout >= 32 and (g.rows // g.n) % 64 == 0
+    return (rn == g.n and sum(cs) == g.cin and g.cin <= GN_IN_CONSUMER_MAX_CHANNELS and g.cin % (64 // g.es) == 0 and g.cout >= 32 and (g.rows // g.n) % 64 == 0
             and g.cin % groups == 0 and all(r <= GN_IN_CONSUMER_MAX_ROWS for r in table_rows) and (not f.vt or _token_gemm_stores_vt(g, f)))
 
 

@@ -20,6 +20,10 @@ extern "C" {
 
 #define GM_F32 0
 #define GM_BF16 1
+/* Limits of a GroupNorm given as the statistic tables of its input's producers (GmConvDesc.pre_stats, gm_linear_rows_gn): rows per table, and input
+ * channels of the (scale | shift) table the consumer builds from them. */
+#define GM_GN_SHORT_MAX_ROWS 128
+#define GM_GN_TABLE_MAX_CHANNELS 384
 
 int gm_abi_version(void);
 const char* gm_last_error(void);
@@ -227,7 +231,7 @@ typedef struct GmConvDesc {
   int ksplit; float* kpartial;
   /* optional GroupNorm prologue given as STATISTICS instead of (pre_scale, pre_shift) -- tile configurations 24 / 25 (conv_sn.hip) and the K slices of a split
    * cfg 11 launch (conv_sk.hip): the consumer folds the per-tile partials of its input (up to two channel-concatenated sources, S_i <= 128 rows
-   * (GN_SHORT_MAX_ROWS) of [N][C_i][2] fp64 each, exactly what gm_gn_finalize_channels takes)
+   * (GM_GN_SHORT_MAX_ROWS) of [N][C_i][2] fp64 each, exactly what gm_gn_finalize_channels takes; cfg 24 / 25 over Cin <= GM_GN_TABLE_MAX_CHANNELS)
    * and forms scale = rstd * gamma, shift = beta - mean * rstd * gamma in its prologue: bit-identical to gm_gn_finalize_channels (reference nn.GroupNorm,
    * diffusion_model_unet.py:671-684), one launch less per norm.  pre_stats[0] == NULL: off. */
   const double* pre_stats[2]; int pre_S[2]; int pre_C[2];
@@ -347,8 +351,8 @@ int gm_linear_rows_affine(const void* x, long long x_ld, const float* pre_scale,
                           int cout, int pre_act, int post_act, int dtype, void* stream);
 /* The same GEMM with the GroupNorm given as the per-tile statistic tables of x's producer(s) instead of (scale, shift): finalised in the GEMM's prologue (the
  * short-table order of gm_gn_finalize_channels: bit-identical to that launch + gm_linear_rows_affine), so an attention block's norm costs no launch of its own
- * (diffusion_model_unet.py:424-441).  stats[i]: [S_i][N][C_i][2] fp64 (sum, sum of squares), S_i <= 128, stats[1] NULL for one source; gamma / beta fp32 over
- * the C0 + C1 = cin <= 384 channels (nullable); rows = n_samples * rows_per_sample, rows_per_sample a multiple of 64; cin a multiple of the MFMA K step (32 bf16 /
+ * (diffusion_model_unet.py:424-441).  stats[i]: [S_i][N][C_i][2] fp64 (sum, sum of squares), S_i <= GM_GN_SHORT_MAX_ROWS, stats[1] NULL for one source; gamma / beta fp32 over
+ * the C0 + C1 = cin <= GM_GN_TABLE_MAX_CHANNELS channels (nullable); rows = n_samples * rows_per_sample, rows_per_sample a multiple of 64; cin a multiple of the MFMA K step (32 bf16 /
  * 16 fp32).  vt != NULL: the V^T image as gm_linear_rows_affine_vt (bf16, no residual). */
 typedef struct GmGnTables {
   const double* stats[2]; int S[2]; int C[2];

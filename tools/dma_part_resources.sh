@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage: res.sh PART [extra flags]  -> per-kernel resource usage of conv_dma.hip part
 P=$1; shift
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -x hip -S --cuda-device-only -DGM_DMA_PART=$P "$@" /root/repo/generativemodels_amd/csrc/conv_dma.hip -o /tmp/p$P.s -Rpass-analysis=kernel-resource-usage 2> /tmp/p$P.remarks
+R="$(cd "$(dirname "$0")/.." && pwd)"
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -I"$R/include" -x hip -S --cuda-device-only -DGM_DMA_PART=$P "$@" "$R/generativemodels_amd/csrc/conv_dma.hip" -o /tmp/p$P.s -Rpass-analysis=kernel-resource-usage 2> /tmp/p$P.remarks
 python - /tmp/p$P.remarks <<'PY'
 import re,sys
 txt=open(sys.argv[1]).read()

@@ -3,7 +3,7 @@ usage: python tools/isa_profile.py conv_dma.hip <mangled-name substring>"""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "generativemodels_amd", "csrc", sys.argv[1])
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result", "-x", "hip", "-S", "--cuda-device-only", src,
+subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result", "-I" + os.path.join(ROOT, "include"), "-x", "hip", "-S", "--cuda-device-only", src,
                 "-o", "/tmp/_isa.s"], capture_output=True, text=True)
 s = open("/tmp/_isa.s").read()
 KEYS = ["valu", "salu", "mfma", "lds", "vmem", "dma", "barrier", "waitcnt", "branch"]

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "generativemodels_amd", "csrc", sys.argv[1])
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 extra = ["-ffp-contract=off"] if sys.argv[1] == "elementwise.hip" else []
-r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result", *extra, "-x", "hip", "-c", src,
+r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result", "-I" + os.path.join(ROOT, "include"), *extra, "-x", "hip", "-c", src,
                     "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
 cur = None
 rows = []
