@@ -27,6 +27,13 @@ class GmGnTables(C.Structure):
                 ("groups", C.c_int)]
 
 
+class GmRowsDesc(C.Structure):
+    _fields_ = [("x", c_vp), ("x_ld", c_ll), ("w", c_vp), ("bias", c_vp), ("res", c_vp), ("res_ld", c_ll), ("y", c_vp), ("y_ld", c_ll),
+                ("rows", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("pre_act", C.c_int), ("post_act", C.c_int), ("dtype", C.c_int),
+                ("pre_scale", c_vp), ("pre_shift", c_vp), ("ss_ld", c_ll), ("gn", C.POINTER(GmGnTables)), ("n_samples", C.c_int),
+                ("rows_per_sample", C.c_int), ("vt", c_vp), ("vt_c0", C.c_int), ("vt_dh", C.c_int)]
+
+
 class GmKlParams(C.Structure):
     _fields_ = [("pred_type", C.c_int), ("c_sa", C.c_float), ("c_sb", C.c_float), ("clip", C.c_int), ("k0", C.c_float),
                 ("k1", C.c_float), ("m0", C.c_float), ("m1", C.c_float), ("t0", C.c_int), ("s", C.c_float), ("e", C.c_float),
@@ -145,13 +152,8 @@ PROTOTYPES = {
     "gm_pack_subpixel_weight": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_attention_max_head_dim": (C.c_int, []),
     "gm_attention_max_wide_head_dim": (C.c_int, []),
-    "gm_linear_rows": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
-    "gm_linear_rows_affine_vt": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, C.c_int, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, C.c_int,
-                                           C.c_int, C.c_int, c_vp]),
-    "gm_linear_rows_gn": (C.c_int, [c_vp, c_ll, C.POINTER(GmGnTables), C.c_int, C.c_int, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
-    "gm_linear_rows_affine": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, C.c_int, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, c_vp]),
+    "gm_rows_gemm": (C.c_int, [C.POINTER(GmRowsDesc), c_vp]),
+    "gm_rows_gemm_route": (C.c_int, [C.POINTER(GmRowsDesc)]),
     "gm_decode_scratch_bytes": (c_ll, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gm_decode_advance": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, c_ll, c_vp]),
     "gm_transformer_decode_step": (C.c_int, [C.POINTER(GmDecodeDesc), c_vp]),

@@ -367,7 +367,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_dma_kernel(const GmAttnDes
 // added in thread order in fp64 and every (block, channel) entry is stored once -- deterministic, and one gn_stats launch less per block.
 #define ATTN_COMBINE_MAX_BLOCKS 256
 // NS: the slice count as a compile-time constant (2 / 4 / 8; 0 = run-time): with a run-time bound hipcc walks the slices one dependent load at a time (two loops: the maxima,
-// then the weighted sums); unrolled, every slice's loads are in flight before the first wait (the same finding as kv_merge_one, small_ops.hip).  Same arithmetic, same order.
+// then the weighted sums); unrolled, every slice's loads are in flight before the first wait (the same finding as kv_merge_one, decode_common.h).  Same arithmetic, same order.
 template <int NS>
 __global__ __launch_bounds__(256) void attn_combine_kernel(const GmAttnDesc p, const float* __restrict__ part, int nsplit_rt) {
   const int nsplit = NS ? NS : nsplit_rt;
@@ -537,7 +537,7 @@ extern "C" int gm_attention_dma_try(const GmAttnDesc* dp, void* stream) {
   const long long vt_bytes = (long long)d.B * d.H * d.dh * lk_pad * 2;
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(d.workspace) + ((vt_bytes + 255) & ~255LL));
   dim3 pg(lk_pad / 64, d.dh / 64, d.B * d.H);
-  if (!d.vt_packed)  // (else: the q | k | v projection stored the image, gm_linear_rows_affine_vt)
+  if (!d.vt_packed)  // (else: the q | k | v projection stored the image, GmRowsDesc.vt)
     vt_pack_kernel<<<pg, 256, 0, st>>>(reinterpret_cast<const bf16_raw*>(d.v), d.v_ld, vt, d.H, d.Lk, lk_pad, d.dh);
   if (d.dh == 64) { if (qf == 2) launch_attn_dma<64, 2>(d, vt, lk_pad, part, sp, st); else launch_attn_dma<64, 1>(d, vt, lk_pad, part, sp, st); }
   else if (d.dh == 128) { if (qf == 2) launch_attn_dma<128, 2>(d, vt, lk_pad, part, sp, st); else launch_attn_dma<128, 1>(d, vt, lk_pad, part, sp, st); }

@@ -1,9 +1,9 @@
 // Pieces shared by the attention kernels (GmAttnDesc / GmAttnBwdDesc themselves: include/gm_amd.h): attention.hip (register-staged, any dtype / head dim),
-// attention_dma.hip (bf16, LDS-DMA), attention_wide.hip, the backward files and the decode step's kernels in small_ops.hip.
+// attention_dma.hip (bf16, LDS-DMA), attention_wide.hip, the backward files and the decode step's kernels in decode_attention.hip and rows_gemm.hip.
 #pragma once
 #include "gm_common.h"
 
-// key ranges of the split-KV single-query attention of the decode step (small_ops.hip; the merge code unrolls over it)
+// key ranges of the split-KV single-query attention of the decode step (decode_attention.hip; the merge code of decode_common.h unrolls over it)
 #define GM_DECODE_KV_SPLITS 16
 // widest head the register-staged kernels serve in one pass (attention.hip), and the widest the sliced kernel serves (attention_wide.hip)
 #define GM_ATTN_MAX_DH 256

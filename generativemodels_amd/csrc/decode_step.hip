@@ -4,7 +4,7 @@
 // residual, LayerNorm + MLP up + GELU, MLP down + residual).  Issued one by one through the Python binding it cost 2.7 ms per token
 // (20 us of interpreter + descriptor work per launch) -- no faster than the reference's recompute-the-prefix loop on this model
 // size.  This entry point walks the block table in C++ and enqueues the kernels back to back.  Round 3: 38 launches where the fused kernels of
-// small_ops.hip take the geometry -- per block [LayerNorm + q|k|v + split-KV attention ranges, its prologue assembling the residual stream from
+// rows_gemm.hip and decode_attention.hip take the geometry -- per block [LayerNorm + q|k|v + split-KV attention ranges, its prologue assembling the residual stream from
 // the previous block's MLP partials] -> [out_proj + residual, its prologue merging the attention ranges] -> [LayerNorm + MLP up + GELU + MLP down
 // as K-slice partials] -- and the round-2 sequence (or a partly fused one) otherwise
 // (reference semantics: networks/nets/transformer.py:98-106, blocks/transformerblock.py:86-91, blocks/selfattention.py:98-147).
@@ -13,7 +13,7 @@
 #include "conv_common.h"
 
 static long long elt(int dtype) { return dtype == GM_F32 ? 4 : 2; }
-// Context windows longer than DECODE_SPLIT_MIN_LEN keys run the single-query attention split over DECODE_KV_SPLITS key ranges (small_ops.hip).
+// Context windows longer than DECODE_SPLIT_MIN_LEN keys run the single-query attention split over DECODE_KV_SPLITS key ranges (decode_attention.hip).
 // The choice depends on the window (max_len), not on the position, so a step issued with a host position and its graph replay agree bit for bit.
 #define DECODE_KV_SPLITS GM_DECODE_KV_SPLITS
 #define DECODE_SPLIT_MIN_LEN 256
@@ -26,10 +26,13 @@ extern "C" long long gm_decode_scratch_bytes(int B, int C, int M, int dtype) {
          r((long long)B * DECODE_KV_SPLITS * 3 * C * 4) + r((long long)((M + 63) / 64) * B * C * 4);  // + the MLP's K-slice partials
 }
 
-// y[rows][cout] = act(x[rows][cin] W^T + b) (+ res) through the small-row GEMM kernel (small_ops.hip)
+// y[rows][cout] = act(x[rows][cin] W^T + b) (+ res) through the row GEMM (rows_gemm.hip), with the fused prologue / epilogue `f` describes (null: none)
 static int linear_rows(const void* x, long long x_ld, const void* w, const float* b, const void* res, long long res_ld, void* y, long long y_ld,
-                       int rows, int cin, int cout, int post_act, int dtype, void* stream) {
-  return gm_linear_rows(x, x_ld, w, b, res, res_ld, y, y_ld, rows, cin, cout, 0, post_act, dtype, stream);
+                       int rows, int cin, int cout, int post_act, int dtype, const GmRowsFused* f, void* stream) {
+  GmRowsDesc r = {};
+  r.x = x; r.x_ld = x_ld; r.w = w; r.bias = b; r.res = res; r.res_ld = res_ld; r.y = y; r.y_ld = y_ld;
+  r.rows = rows; r.cin = cin; r.cout = cout; r.post_act = post_act; r.dtype = dtype;
+  return gm_rows_gemm_fused(&r, f, stream);
 }
 
 // ---- the route plan ---------------------------------------------------------------------------------------------------------------------
@@ -37,7 +40,7 @@ static int linear_rows(const void* x, long long x_ld, const void* w, const float
 // by the GM_DECODE_PLAN_* names of include/gm_amd.h.  gm_transformer_decode_step consults it per block; gm_transformer_decode_plan exports it.
 // The decisions depend on the geometry, the dtype, null-ness of pointers and host-or-device position only -- never on the position itself.
 static bool decode_mlp_fused(const GmDecodeDesc& d) {
-  // the MLP as one launch leaving M / 64 K-slice partials that the next launch's prologue sums with the residual row (small_ops.hip)
+  // the MLP as one launch leaving M / 64 K-slice partials that the next launch's prologue sums with the residual row (rows_gemm.hip)
   bool mlp_fuse = gm_mlp_rows_fusable(d.B, d.C, d.M, d.dtype) == 1;
   for (int i = 0; i < d.depth; ++i) mlp_fuse = mlp_fuse && d.blocks[i].ln3_g;  // (its staging pass is the LayerNorm)
   return mlp_fuse;
@@ -147,7 +150,7 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
     int plan[GM_DECODE_PLAN_COUNT];
     decode_plan(d, i, qa, mlp_fuse, plan);
     const bool split = plan[GM_DECODE_PLAN_SPLIT_KV] != 0;
-    // LayerNorm + q | k | v + the attention ranges as ONE launch where that kernel takes the geometry (small_ops.hip: qkv_attn_rows_kernel) ...
+    // LayerNorm + q | k | v + the attention ranges as ONE launch where that kernel takes the geometry (decode_attention.hip: qkv_attn_rows_kernel) ...
     bool qkv_done = false;
     if (plan[GM_DECODE_PLAN_QKV_NG]) {
       qa.pos = hpos;
@@ -160,15 +163,15 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
     // Behind a fused MLP the launch first assembles its input x0 = x1 + b2 + sum_j P[j] (and stores it: the out-projection below adds it as the residual)
     char* kdst = reinterpret_cast<char*>(b.k_cache) + (long long)hpos * C * es;
     char* vdst = reinterpret_cast<char*>(b.v_cache) + (long long)hpos * C * es;
-    if (qkv_done)
-      rc = 0;
-    else if (plan[GM_DECODE_PLAN_QKV_INPUT] == GM_DECODE_INPUT_MLP_MERGE)
-      rc = gm_linear_rows_mlpmerge(mlp_p, mlp_nj, x1, d.blocks[i - 1].b_2, x0, b.ln1_g, b.ln1_b, d.ln_eps, b.w_qkv, b.b_qkv, qkv, 3 * C, kdst, vdst,
-                                   (long long)d.max_len * C, C, d.B, C, 3 * C, 0, d.dtype, d.pos_dev, C, stream);
-    else
-      rc = gm_linear_rows_ln(x0, C, b.ln1_g, b.ln1_b, d.ln_eps, b.w_qkv, b.b_qkv, qkv, 3 * C, kdst, vdst, (long long)d.max_len * C, C, d.B, C, 3 * C,
-                             0, d.dtype, d.pos_dev, C, stream);
-    if (rc) return rc;
+    if (!qkv_done) {
+      const bool merge_in = plan[GM_DECODE_PLAN_QKV_INPUT] == GM_DECODE_INPUT_MLP_MERGE;
+      GmRowsFused fz = {};
+      fz.ln_g = b.ln1_g; fz.ln_b = b.ln1_b; fz.ln_eps = d.ln_eps;
+      fz.y1 = kdst; fz.y2 = vdst; fz.y12_ld = (long long)d.max_len * C; fz.split = C;
+      fz.off_dev = d.pos_dev; fz.off_mul = C;
+      if (merge_in) { fz.mlp_p = mlp_p; fz.mlp_nj = mlp_nj; fz.mlp_x1 = x1; fz.mlp_b2 = d.blocks[i - 1].b_2; fz.mlp_x0 = x0; }
+      if ((rc = linear_rows(merge_in ? nullptr : x0, merge_in ? 0 : C, b.w_qkv, b.b_qkv, nullptr, 0, qkv, 3 * C, d.B, C, 3 * C, 0, d.dtype, &fz, stream))) return rc;
+    }
     GmAttnDesc at = {};
     at.q = qkv; at.q_ld = 3 * C;
     at.k = b.k_cache; at.k_ld = C; at.k_bs = (long long)d.max_len * C;
@@ -178,32 +181,37 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
     at.scale = scale; at.dtype = d.dtype;
     bool out_done = false;
     if (split) {
-      // the partials are merged by the out-projection's prologue where its K-split kernel applies, by a combine launch otherwise: the two
-      // forms give the same bits, and which one runs depends on the geometry only
-      const bool fuse = plan[GM_DECODE_PLAN_OUT_MERGE] == GM_DECODE_MERGE_OUT_PROJ;
+      // the partials are merged by the out-projection's prologue where its K-split kernel applies (the plan's decision: the launcher refuses a
+      // geometry outside that kernel), by a combine launch otherwise: the two forms give the same bits, and which one runs depends on the geometry only
       if (!qkv_done)
         GM_REQUIRE(gm_attention_decode_split(&at, d.pos_dev, kv_ws, DECODE_KV_SPLITS, 0, d.max_len, stream) == 1, "head size beyond the single-query attention kernels");
-      rc = fuse ? gm_linear_rows_kvmerge(kv_ws, DECODE_KV_SPLITS, at.dh, b.w_o, b.b_o, x0, C, x1, C, d.B, C, C, d.dtype, stream) : 0;
-      if (rc < 0) return rc;
-      GM_REQUIRE((rc == 1) == fuse, "the partial-merging out-projection disagrees with the plan");
-      out_done = rc == 1;
-      if (!out_done) GM_REQUIRE(gm_attention_decode_split(&at, d.pos_dev, kv_ws, DECODE_KV_SPLITS, 2, d.max_len, stream) == 1, "merge of the attention partials");
+      if (plan[GM_DECODE_PLAN_OUT_MERGE] == GM_DECODE_MERGE_OUT_PROJ) {
+        GmRowsFused fz = {};
+        fz.kv_ws = kv_ws; fz.kv_ns = DECODE_KV_SPLITS; fz.kv_dh = at.dh;
+        if ((rc = linear_rows(nullptr, 0, b.w_o, b.b_o, x0, C, x1, C, d.B, C, C, 0, d.dtype, &fz, stream))) return rc;
+        out_done = true;
+      } else {
+        GM_REQUIRE(gm_attention_decode_split(&at, d.pos_dev, kv_ws, DECODE_KV_SPLITS, 2, d.max_len, stream) == 1, "merge of the attention partials");
+      }
     } else if (plan[GM_DECODE_PLAN_ATTN_ENTRY] == GM_DECODE_ENTRY_DEVICE_POS) {
       GM_REQUIRE(gm_attention_decode_dev(&at, d.pos_dev, stream) == 1, "context window too long for the single-query attention kernel");
     } else if ((rc = gm_attention_forward(&at, stream))) {
       return rc;
     }
-    if (!out_done && (rc = linear_rows(y, C, b.w_o, b.b_o, x0, C, x1, C, d.B, C, C, 0, d.dtype, stream))) return rc;
+    if (!out_done && (rc = linear_rows(y, C, b.w_o, b.b_o, x0, C, x1, C, d.B, C, C, 0, d.dtype, nullptr, stream))) return rc;
     if (mlp_fuse) {
       if ((rc = gm_mlp_rows(x1, b.ln3_g, b.ln3_b, d.ln_eps, b.w_1, b.b_1, b.w_2, mlp_p, d.B, C, d.M, 6, d.dtype, stream))) return rc;
       continue;
     }
-    if ((rc = gm_linear_rows_ln(x1, C, b.ln3_g, b.ln3_b, d.ln_eps, b.w_1, b.b_1, a, d.M, nullptr, nullptr, 0, 0, d.B, C, d.M, 6, d.dtype,
-                                nullptr, 0, stream))) return rc;
-    if ((rc = linear_rows(a, d.M, b.w_2, b.b_2, x1, C, x0, C, d.B, d.M, C, 0, d.dtype, stream))) return rc;
+    GmRowsFused ln3 = {};
+    ln3.ln_g = b.ln3_g; ln3.ln_b = b.ln3_b; ln3.ln_eps = d.ln_eps;
+    if ((rc = linear_rows(x1, C, b.w_1, b.b_1, nullptr, 0, a, d.M, d.B, C, d.M, 6, d.dtype, &ln3, stream))) return rc;
+    if ((rc = linear_rows(a, d.M, b.w_2, b.b_2, x1, C, x0, C, d.B, d.M, C, 0, d.dtype, nullptr, stream))) return rc;
   }
-  if (mlp_fuse)
-    return gm_linear_rows_mlpmerge(mlp_p, mlp_nj, x1, d.blocks[d.depth - 1].b_2, nullptr, nullptr, nullptr, 0.f, d.w_logits, d.b_logits, d.logits,
-                                   d.num_tokens, nullptr, nullptr, 0, 0, d.B, C, d.num_tokens, 0, d.dtype, nullptr, 0, stream);
-  return linear_rows(x0, C, d.w_logits, d.b_logits, nullptr, 0, d.logits, d.num_tokens, d.B, C, d.num_tokens, 0, d.dtype, stream);
+  if (mlp_fuse) {  // to_logits assembles its input from the last block's MLP partials
+    GmRowsFused fz = {};
+    fz.mlp_p = mlp_p; fz.mlp_nj = mlp_nj; fz.mlp_x1 = x1; fz.mlp_b2 = d.blocks[d.depth - 1].b_2;
+    return linear_rows(nullptr, 0, d.w_logits, d.b_logits, nullptr, 0, d.logits, d.num_tokens, d.B, C, d.num_tokens, 0, d.dtype, &fz, stream);
+  }
+  return linear_rows(x0, C, d.w_logits, d.b_logits, nullptr, 0, d.logits, d.num_tokens, d.B, C, d.num_tokens, 0, d.dtype, nullptr, stream);
 }

@@ -53,22 +53,27 @@ int gm_attention_dma_try(const GmAttnDesc* dp, void* stream);
 int gm_embed_tokens_dev(const long long* indices, const void* token_weight, const void* position_weight, void* out, long long batch, int seq_len, int C,
                         int pos0, int num_tokens, int max_positions, int dtype, const int* pos_dev, void* stream);
 
-// ---- small_ops.hip: the kernels of the decode step (decode_step.hip) -- single-query attention, row GEMMs with fused prologues, the fused MLP
-int gm_attention_decode_try(const GmAttnDesc* dp, void* stream);
-int gm_attention_decode_dev(const GmAttnDesc* dp, const int* lk_dev, void* stream);
-int gm_attention_decode_split(const GmAttnDesc* dp, const int* lk_dev, float* ws, int nsplit, int merge, int cap, void* stream);
+// ---- rows_gemm.hip: the row GEMMs with the decode step's fused prologues and epilogues (decode_step.hip), and the fused MLP
 int gm_linear_rows_takes_ksplit(int rows, int cin, int dtype);
-int gm_linear_rows_ln(const void* x, long long x_ld, const float* ln_g, const float* ln_b, float ln_eps, const void* w, const float* bias, void* y,
-                      long long y_ld, void* y1, void* y2, long long y12_ld, int split, int rows, int cin, int cout, int post_act, int dtype,
-                      const int* off_dev, long long off_mul, void* stream);
-int gm_linear_rows_kvmerge(const float* kv_ws, int kv_ns, int kv_dh, const void* w, const float* bias, const void* res, long long res_ld, void* y,
-                           long long y_ld, int rows, int cin, int cout, int dtype, void* stream);
-int gm_linear_rows_mlpmerge(const float* P, int nj, const void* x1, const float* b2, void* x0_out, const float* ln_g, const float* ln_b, float ln_eps,
-                            const void* w, const float* bias, void* y, long long y_ld, void* y1, void* y2, long long y12_ld, int split, int rows, int cin,
-                            int cout, int post_act, int dtype, const int* off_dev, long long off_mul, void* stream);
+// What the decode step adds to a plain GmRowsDesc (whose x is NULL with a partial source); every group is off when its first member is 0 / null.
+struct GmRowsFused {
+  const float* ln_g; const float* ln_b; float ln_eps;  // x <- LayerNorm(x) * g + b before the GEMM
+  void* y1; void* y2; long long y12_ld; int split;     // cout = 3 * split: channels [split, 2 split) -> y1, [2 split, 3 split) -> y2 (row pitch y12_ld) ...
+  const int* off_dev; long long off_mul;               // ... advanced by (*off_dev) * off_mul elements at run time (KV-cache row = position)
+  const float* kv_ws; int kv_ns, kv_dh;                // x = the merge of the split-KV attention partials (gm_attention_decode_split, merge 0): kv_ns ranges, head size kv_dh
+  const float* mlp_p; int mlp_nj; const void* mlp_x1; const float* mlp_b2; void* mlp_x0;  // x = x1 + b2 + sum_j P[j] over gm_mlp_rows's nj partials, stored to mlp_x0 when given
+};
+// gm_rows_gemm with those extras (f NULL: none).  The two partial sources exist in the K-split kernel only: a geometry outside it is an error.
+int gm_rows_gemm_fused(const GmRowsDesc* d, const GmRowsFused* f, void* stream);
+// The decode step's MLP as one launch leaving (M / 64) * rows * C fp32 K-slice partials in P for GmRowsFused.mlp_p; fusable: 1 when both kernels take the geometry.
 int gm_mlp_rows_fusable(int rows, int C, int M, int dtype);
 int gm_mlp_rows(const void* x, const float* ln_g, const float* ln_b, float ln_eps, const void* w1, const float* b1, const void* w2, float* P, int rows,
                 int C, int M, int act, int dtype, void* stream);
+
+// ---- decode_attention.hip: one query per (batch, head) over a KV cache -- single launch, split over key ranges, or fused behind the q | k | v projection
+int gm_attention_decode_try(const GmAttnDesc* dp, void* stream);
+int gm_attention_decode_dev(const GmAttnDesc* dp, const int* lk_dev, void* stream);
+int gm_attention_decode_split(const GmAttnDesc* dp, const int* lk_dev, float* ws, int nsplit, int merge, int cap, void* stream);
 // LayerNorm + q | k | v + one key range of the single-query attention in one launch (qkv_attn_rows_kernel, which takes the struct by value)
 struct QkvAttnArgs {
   const void* x0;                                                       // [B][C] rows, or null with the partial source below

@@ -2,6 +2,7 @@
 //   gm_embed_tokens   token + absolute position embedding            (reference: networks/nets/transformer.py:99-101)
 //   gm_sample_probs   the sampling head: temperature, top-k crop, softmax, BOS probability zeroed
 //                                                                    (reference: inferers/inferer.py:1221-1232)
+//   gm_sample_index   one categorical draw per row by inverse CDF      (reference: inferers/inferer.py:1235)
 //   gm_token_log_prob log(softmax(logits)[target]) per row           (reference: inferers/inferer.py:1290-1296, 1310-1316)
 // One wave per row; the vocabulary (num_embeddings + 1, a few hundred to a few thousand entries) is walked by the 64 lanes.
 #include "gm_common.h"
@@ -147,6 +148,61 @@ extern "C" int gm_sample_probs(const void* logits, long long ld, float* probs, l
     sample_probs_kernel<bf16_raw><<<(unsigned)rows, 64, 0, st>>>((const bf16_raw*)logits, ld, probs, V, temperature, top_k, bos_index);
   else
     GM_FAIL(-2, "unsupported dtype");
+  GM_LAUNCH_CHECK();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// One categorical draw per row by inverse CDF: idx = min{ j : sum_{i <= j} p_i >= u * sum_i p_i }, u uniform in [0, 1) supplied by
+// the caller's generator.  torch.multinomial validates its input with a device -> host read, i.e. one pipeline drain per sampled
+// token (1.5 ms per token in tools/diag_c5.py); this kernel keeps the sampling loop asynchronous.  One wave per row.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void sample_index_kernel(const float* __restrict__ probs, int V, const float* __restrict__ u,
+                                                         long long* __restrict__ out) {
+  const long long row = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float* pr = probs + row * (long long)V;
+  const int per = (V + 63) / 64, j0 = lane * per, j1 = min(V, j0 + per);
+  float loc = 0.f;
+  for (int j = j0; j < j1; ++j) loc += pr[j];
+  float incl = loc;  // inclusive scan over lanes
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  const float total = __shfl(incl, 63, 64);
+  const float target = u[row] * total;
+  const float excl = incl - loc;
+  // the first lane whose inclusive sum reaches the target owns the draw; rounding can leave no such lane: take the last non-empty
+  const bool mine = (incl >= target) && (excl <= target) && loc > 0.f;
+  unsigned long long ballot = __ballot(mine);
+  int idx = -1;
+  if (ballot) {
+    const int owner = __ffsll((long long)ballot) - 1;
+    if (lane == owner) {
+      // (this running sum starts from excl = incl - loc, a rounded difference: it can end an ulp below incl, and then below a target the
+      //  ballot accepted -- the draw is the lane's last entry of positive probability, never a zero-probability one behind it)
+      float c = excl;
+      for (int j = j0; j < j1; ++j) {
+        c += pr[j];
+        if (pr[j] > 0.f) { idx = j; if (c >= target) break; }
+      }
+      out[row] = idx;
+    }
+  } else {
+    // target beyond the accumulated total (u ~ 1 with rounding): the last entry with positive probability
+    int last = -1;
+    for (int j = j0; j < j1; ++j) if (pr[j] > 0.f) last = j;
+    for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if (lane == 0) out[row] = last < 0 ? 0 : last;
+  }
+}
+
+extern "C" int gm_sample_index(const float* probs, long long rows, int V, const float* u, long long* out, void* stream) {
+  GM_REQUIRE(probs && u && out, "null pointer");
+  GM_REQUIRE(V > 0, "empty vocabulary");
+  if (rows == 0) return 0;
+  GM_REQUIRE(rows < (1LL << 31), "too many rows");
+  sample_index_kernel<<<(unsigned)rows, 64, 0, (hipStream_t)stream>>>(probs, V, u, out);
   GM_LAUNCH_CHECK();
 }
 

@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native as nat
-from ._native import GmAttnBwdDesc, GmAttnDesc, GmConvDesc, GmDftDesc, GmGnTables, GmKlParams, GmResizeDesc, GmStepParams, GmWgradDesc, check, lib
+from ._native import GmAttnBwdDesc, GmAttnDesc, GmConvDesc, GmDftDesc, GmGnTables, GmKlParams, GmResizeDesc, GmRowsDesc, GmStepParams, GmWgradDesc, check, lib
 from .resize_plan import ResizePlan, plan_for
 from .spectral_plan import SpectralPlan, device_twiddles
 from .spectral_plan import plan_for as spectral_plan_for
@@ -984,12 +984,12 @@ _CONV_DEBUG_FLAGS = 0  # tools/bench_conv.py ablations only
 _SK_STAMPS = None  # tools/sk_timeline.py: the stamp table of the last split-K launch (debug_flags bit 12)
 _CONV_TIMELINE_BUFFER = None  # tools/conv_timeline.py (bench-only -DGM_CONV_TIMELINE build): int64 [work-groups, 64] stamp table
 
-SMALL_LINEAR_ROWS = 64       # 1x1 "convolutions" over at most this many rows take gm_linear_rows
+SMALL_LINEAR_ROWS = 64       # 1x1 "convolutions" over at most this many rows take the one-block-per-wave row GEMM (gm_rows_gemm)
 # 1x1 convolutions over token rows (the GN-prologue q|k|v projections of the latent-resolution attention blocks and their gradients): the tiled
-# kernels cost ~20 us per launch there whatever the size (a stage -> barrier -> tap -> barrier chain per K chunk); gm_linear_rows_affine requests
+# kernels cost ~20 us per launch there whatever the size (a stage -> barrier -> tap -> barrier chain per K chunk); gm_rows_gemm requests
 # all K chunks of a 16 x 16 output block straight from L2.  Bounds: what was measured (tools/bench_conv1x1.py)
 TOKEN_GEMM = os.environ.get("GM_TOKEN_GEMM", "1") != "0"
-TOKEN_GEMM_MAX_ROWS = int(os.environ.get("GM_TOKEN_GEMM_MAX_ROWS", "32768"))  # (8192 until the wide form of round 6: small_ops.hip token_gemm_wide_kernel)
+TOKEN_GEMM_MAX_ROWS = int(os.environ.get("GM_TOKEN_GEMM_MAX_ROWS", "32768"))  # (8192 until the wide form of round 6: rows_gemm.hip token_gemm_wide_kernel)
 TOKEN_GEMM_MAX_CIN = 512
 TOKEN_GEMM_MAX_FLOP = 2.0e9
 DMA_CONV = True              # route eligible 3x3x3 convolutions through conv_dma.hip (cfg 11)
@@ -1238,14 +1238,28 @@ def _takes_small_rows(g: ConvGeometry, f: ConvFacts) -> bool:
             and g.plo == _ZEROS and g.phi == _ZEROS)
 
 
-def _launch_small_rows(g, f, x, panel, bias, pre_act, res, post_act, out):
-    dtype = x.dtype
-    out, out_ld = _out_and_res((*x.shape[:-1], g.cout), dtype, x.device, out, res)
+def _rows_desc(g, f, x, bias, pre_act, res, post_act, out):
+    """-> (out, the GmRowsDesc of the plain row GEMM over x, the fp32 bias to keep alive until the launch).  The token GEMM adds its prologue and the V^T image;
+    _rows_gemm adds the weight panel."""
+    out, out_ld = _out_and_res((*x.shape[:-1], g.cout), x.dtype, x.device, out, res)
     b32 = as_f32(bias)
-    _timed(f"linear_rows<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * g.rows * g.cin * g.cout, bytes=float(g.es * g.cin * g.cout), shape=f"{g.rows}x{g.cin}->{g.cout}"),
-           lambda: check(lib().gm_linear_rows(x.data_ptr(), f.x_ld, panel().data_ptr(), _ptr(b32), _ptr(res), 0 if res is None else arena_ld(res),
-                                              out.data_ptr(), out_ld, g.rows, g.cin, g.cout, ACT[pre_act], POST_ACT[post_act], dt_code(dtype),
-                                              _stream()), "gm_linear_rows"))
+    d = GmRowsDesc()
+    d.x, d.x_ld, d.bias, d.y, d.y_ld = x.data_ptr(), f.x_ld, _ptr(b32), out.data_ptr(), out_ld
+    if res is not None:
+        d.res, d.res_ld = res.data_ptr(), arena_ld(res)
+    d.rows, d.cin, d.cout, d.pre_act, d.post_act, d.dtype = g.rows, g.cin, g.cout, ACT[pre_act], POST_ACT[post_act], dt_code(x.dtype)
+    return out, d, b32
+
+
+def _rows_gemm(d, panel):
+    d.w = panel().data_ptr()  # (packed on first use: inside the timed region, like every other launch)
+    check(lib().gm_rows_gemm(C.byref(d), _stream()), "gm_rows_gemm")
+
+
+def _launch_small_rows(g, f, x, panel, bias, pre_act, res, post_act, out):
+    out, d, b32 = _rows_desc(g, f, x, bias, pre_act, res, post_act, out)  # noqa: F841 -- b32 alive until the launch
+    _timed(f"linear_rows<{str(x.dtype).split('.')[-1]}>", dict(flops=2.0 * g.rows * g.cin * g.cout, bytes=float(g.es * g.cin * g.cout), shape=f"{g.rows}x{g.cin}->{g.cout}"),
+           lambda: _rows_gemm(d, panel))
     return out
 
 
@@ -1295,46 +1309,36 @@ def _token_gemm_takes_recipe(g: ConvGeometry, f: ConvFacts) -> bool:
 
 def _launch_token_gemm(g, f, x, panel, bias, pre, pre_act, res, post_act, out, vt):
     """-> (out, launched).  Not launched: (scale, shift) tables the kernels cannot read as vectors -- the caller goes on to the tile kernels with `out` allocated."""
-    dtype, n, rows, cin, cout = x.dtype, g.n, g.rows, g.cin, g.cout
-    out, out_ld = _out_and_res((*x.shape[:-1], cout), dtype, x.device, out, res)
-    b32 = as_f32(bias)
+    n, rows, cin, cout = g.n, g.rows, g.cin, g.cout
+    out, d, b32 = _rows_desc(g, f, x, bias, pre_act, res, post_act, out)  # noqa: F841 -- b32 alive until the launch
+    d.rows_per_sample = rows // n
     store_vt = _token_gemm_stores_vt(g, f)
-    vws, vt_c0, vt_dh = vt if store_vt else (None, 0, 0)
-    res_ld = 0 if res is None else arena_ld(res)
-
-    def launch(form, name, call):
-        if _PROFILE is None:
-            check(call(), name)
-        else:
-            _timed(f"token_gemm<{str(dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(g.es * (rows * (cin + cout) + cin * cout)),
-                                                                  shape=f"{rows}x{cin}->{cout}{form}"), lambda: check(call(), name))
-        if store_vt:
-            out._gm_vt_packed = True
-        return out, True
+    form = " (+V^T image)" if store_vt else ""
+    if store_vt:
+        d.vt, d.vt_c0, d.vt_dh = vt[0].data_ptr(), int(vt[1]), int(vt[2])
     if _token_gemm_takes_recipe(g, f):
         t = GmGnTables()
         for i, st in enumerate(pre.stats):
             t.stats[i], t.S[i], t.C[i] = st.data_ptr(), st.shape[0], pre.cs[i]
         t.gamma, t.beta, t.eps, t.groups = _ptr(pre.gamma), _ptr(pre.beta), pre.eps, pre.groups
-        return launch(f" (GroupNorm from statistics{' +V^T image' if store_vt else ''})", "gm_linear_rows_gn", lambda: lib().gm_linear_rows_gn(
-            x.data_ptr(), f.x_ld, C.byref(t), n, rows // n, panel().data_ptr(), _ptr(b32), _ptr(res), res_ld, out.data_ptr(), out_ld, rows, cin, cout,
-            ACT[pre_act], POST_ACT[post_act], _ptr(vws), int(vt_c0), int(vt_dh), dt_code(dtype), _stream()))
-    sc = sh = None
-    if pre is not None:
+        d.gn, d.n_samples = C.pointer(t), n
+        form = f" (GroupNorm from statistics{' +V^T image' if store_vt else ''})"
+    elif pre is not None:
         sc, sh = pre
         if sc.dtype != torch.float32 or sh.dtype != torch.float32 or sc.shape != (n, cin) or sh.shape != (n, cin) or sc.stride(-1) != 1 or sh.stride(-1) != 1 \
                 or sc.stride(0) != sh.stride(0):
             raise ValueError("pre = (scale, shift): fp32 [N, Cin] tables with a common row pitch")
         if not (sc.stride(0) % 4 == 0 and sc.data_ptr() % 16 == 0 and sh.data_ptr() % 16 == 0):
             return out, False
-    pitch = 0 if sc is None else sc.stride(0)
+        d.pre_scale, d.pre_shift, d.ss_ld = sc.data_ptr(), sh.data_ptr(), sc.stride(0)
+    if _PROFILE is None:
+        _rows_gemm(d, panel)
+    else:
+        _timed(f"token_gemm<{str(x.dtype).split('.')[-1]}>", dict(flops=2.0 * rows * cin * cout, bytes=float(g.es * (rows * (cin + cout) + cin * cout)),
+                                                                shape=f"{rows}x{cin}->{cout}{form}"), lambda: _rows_gemm(d, panel))
     if store_vt:
-        return launch(" (+V^T image)", "gm_linear_rows_affine_vt", lambda: lib().gm_linear_rows_affine_vt(
-            x.data_ptr(), f.x_ld, _ptr(sc), _ptr(sh), pitch, rows // n, panel().data_ptr(), _ptr(b32), out.data_ptr(), out_ld, rows, cin, cout,
-            ACT[pre_act], vws.data_ptr(), int(vt_c0), int(vt_dh), dt_code(dtype), _stream()))
-    return launch("", "gm_linear_rows_affine", lambda: lib().gm_linear_rows_affine(
-        x.data_ptr(), f.x_ld, _ptr(sc), _ptr(sh), pitch, rows // n, panel().data_ptr(), _ptr(b32), _ptr(res), res_ld, out.data_ptr(), out_ld, rows, cin,
-        cout, ACT[pre_act], POST_ACT[post_act], dt_code(dtype), _stream()))
+        out._gm_vt_packed = True
+    return out, True
 
 
 def _subpixel_operands(g: ConvGeometry, f: ConvFacts) -> bool:

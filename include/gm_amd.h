@@ -20,7 +20,7 @@ extern "C" {
 
 #define GM_F32 0
 #define GM_BF16 1
-/* Limits of a GroupNorm given as the statistic tables of its input's producers (GmConvDesc.pre_stats, gm_linear_rows_gn): rows per table, and input
+/* Limits of a GroupNorm given as the statistic tables of its input's producers (GmConvDesc.pre_stats, GmRowsDesc.gn): rows per table, and input
  * channels of the (scale | shift) table the consumer builds from them. */
 #define GM_GN_SHORT_MAX_ROWS 128
 #define GM_GN_TABLE_MAX_CHANNELS 384
@@ -52,8 +52,8 @@ int gm_sched_step(const void* sample, const void* model_output, const void* nois
 /* The register-staged attention kernel (fp32; bf16 outside the LDS-DMA kernel's geometries: causal, few keys, head dim 32) deals the key tiles of a work-group to
  * g = 1, 2 or 4 groups of four waves (4: fp32 at head dim <= 64 only, else 2); anything else = by key-tile count (the default: 2 from four tiles, 4 from eight).  Process-wide, for measurements and tests. */
 void gm_attention_set_wave_groups(int g);
-/* The affine token GEMMs (gm_linear_rows_affine / _vt, gm_linear_rows) over at least `min_rows` rows run with a wave owning 16 rows x nb * 16 output channels
- * (nb = 2, 3 or 4, anything else = chosen by the row count; small_ops.hip: token_gemm_wide_kernel) instead of one 16-channel block per wave.  min_rows 0 = never,
+/* The row GEMMs (gm_rows_gemm) over at least `min_rows` rows run with a wave owning 16 rows x nb * 16 output channels
+ * (nb = 2, 3 or 4, anything else = chosen by the row count; rows_gemm.hip: token_gemm_wide_kernel, GM_ROWS_ROUTE_WIDE) instead of one 16-channel block per wave.  min_rows 0 = never,
  * < 0 = the default (2048): a process-wide switch for measurements and tests; results are bit-identical either way. */
 void gm_token_gemm_set_wide(int min_rows, int nb);
 /* out[0..n) = torch.randn(n, dtype=torch.bfloat16) of the CPU generator -- the noise DDPMScheduler.step / DDIMScheduler.step (eta > 0) draw for a bf16 chain
@@ -291,7 +291,7 @@ typedef struct GmAttnDesc {
                                * the stored output (+ residual) for the GroupNorm that follows an attention block (plain stores, one per block and
                                * channel); must be NULL when gm_attention_stats_slots() returns 0 for this geometry */
   int vt_packed;              /* 1: `workspace` already holds the transposed, key-permuted V image of the LDS-DMA kernel -- the stacked q | k | v projection
-                               * wrote it (gm_linear_rows_affine_vt; Lk a multiple of 64): the pack launch is skipped.  Only with a workspace of
+                               * wrote it (GmRowsDesc.vt; Lk a multiple of 64): the pack launch is skipped.  Only with a workspace of
                                * gm_attention_workspace_bytes() > 0 bytes */
   float* lse;                 /* optional fp32 [B*H][Lq]: log sum_k exp(scale q.k) per query, written by the LDS-DMA path only (must be NULL otherwise);
                                * the training forward keeps it for gm_attention_backward_fused */
@@ -332,37 +332,46 @@ int gm_sample_index(const float* probs, long long rows, int V, const float* u, l
 int gm_token_log_prob(const void* logits, long long ld, const long long* target, float* out, long long rows, int V, int dtype,
                       void* stream);
 
-/* y[rows][cout] = post_act(pre_act(x)[rows][cin] W^T + bias) (+ res) for a handful of rows (decode steps, the timestep MLP): one wave
- * per 16 output channels, weights global -> registers -> MFMA, no LDS.  w: gm_pack_conv_weight image of the [cout][cin] matrix;
- * pre_act / post_act as in GmConvDesc; cin and x_ld multiples of 16 bytes. */
-int gm_linear_rows(const void* x, long long x_ld, const void* w, const float* bias, const void* res, long long res_ld, void* y,
-                   long long y_ld, int rows, int cin, int cout, int pre_act, int post_act, int dtype, void* stream);
-/* The same over token rows with a per-sample GroupNorm affine in front: y = post_act(pre_act(x * scale[n] + shift[n]) W^T + bias) (+ res),
- * n = row / rows_per_sample, scale / shift fp32 [N][ss_ld] (both null: no affine).  The GroupNorm -> q | k | v projection of the
- * latent-resolution AttentionBlocks (diffusion_model_unet.py:395-405) and the other 1x1 convolutions over a few thousand tokens. */
-/* gm_linear_rows_affine as the stacked q | k | v projection of an attention block (diffusion_model_unet.py:407-415): the V columns (output channels
- * >= vt_c0, heads of vt_dh channels) are also stored as the V^T image of the LDS-DMA attention kernel at the head of its workspace; bf16,
- * rows_per_sample (tokens per sample) a multiple of 64 */
-int gm_linear_rows_affine_vt(const void* x, long long x_ld, const float* pre_scale, const float* pre_shift, long long ss_ld, int rows_per_sample,
-                             const void* w, const float* bias, void* y, long long y_ld, int rows, int cin, int cout, int pre_act, void* vt,
-                             int vt_c0, int vt_dh, int dtype, void* stream);
-int gm_linear_rows_affine(const void* x, long long x_ld, const float* pre_scale, const float* pre_shift, long long ss_ld, int rows_per_sample,
-                          const void* w, const float* bias, const void* res, long long res_ld, void* y, long long y_ld, int rows, int cin,
-                          int cout, int pre_act, int post_act, int dtype, void* stream);
-/* The same GEMM with the GroupNorm given as the per-tile statistic tables of x's producer(s) instead of (scale, shift): finalised in the GEMM's prologue (the
- * short-table order of gm_gn_finalize_channels: bit-identical to that launch + gm_linear_rows_affine), so an attention block's norm costs no launch of its own
- * (diffusion_model_unet.py:424-441).  stats[i]: [S_i][N][C_i][2] fp64 (sum, sum of squares), S_i <= GM_GN_SHORT_MAX_ROWS, stats[1] NULL for one source; gamma / beta fp32 over
- * the C0 + C1 = cin <= GM_GN_TABLE_MAX_CHANNELS channels (nullable); rows = n_samples * rows_per_sample, rows_per_sample a multiple of 64; cin a multiple of the MFMA K step (32 bf16 /
- * 16 fp32).  vt != NULL: the V^T image as gm_linear_rows_affine_vt (bf16, no residual). */
+/* ---- row GEMM: nn.Linear and the 1x1 convolutions over tokens (diffusion_model_unet.py:395-415, 1758-1760; transformer blocks) ----------------
+ * The statistic tables of a GroupNorm whose finalisation runs in its consumer's prologue: stats[i] = [S_i][N][C_i][2] fp64 (sum, sum of squares) of x's
+ * producer(s), S_i <= GM_GN_SHORT_MAX_ROWS, stats[1] NULL for one source; gamma / beta fp32 over the C0 + C1 channels (nullable). */
 typedef struct GmGnTables {
   const double* stats[2]; int S[2]; int C[2];
   const float* gamma; const float* beta; float eps; int groups;
 } GmGnTables;
-int gm_linear_rows_gn(const void* x, long long x_ld, const GmGnTables* gn, int n_samples, int rows_per_sample, const void* w, const float* bias,
-                      const void* res, long long res_ld, void* y, long long y_ld, int rows, int cin, int cout, int pre_act, int post_act, void* vt,
-                      int vt_c0, int vt_dh, int dtype, void* stream);
+/* y[rows][cout] = post_act(pre_act(norm(x))[rows][cin] W^T + bias) (+ res), without the tiled convolution's LDS loop: a handful of rows (decode steps, the
+ * timestep MLP) up to a few thousand token rows (the q | k | v and output projections of the latent-resolution AttentionBlocks).
+ *   x, w, bias, res, y    w = the gm_pack_conv_weight image of the [cout][cin] matrix; bias fp32 [cout] or NULL; res NULL or rows of pitch res_ld; cin and x_ld
+ *                         multiples of 16 bytes, x 16-byte aligned; pre_act / post_act as in GmConvDesc
+ *   norm, at most one of  pre_scale / pre_shift (both or neither): x * scale[n] + shift[n] with n = row / rows_per_sample, fp32 [N][ss_ld] tables of 16-byte
+ *                         aligned rows (ss_ld a multiple of 4), rows_per_sample > 0
+ *                         gn: the same GroupNorm given as statistic tables and finalised in the GEMM's prologue, in the short-table order of
+ *                         gm_gn_finalize_channels (bit-identical to that launch + the (scale, shift) form), so an attention block's norm costs no launch of
+ *                         its own (diffusion_model_unet.py:424-441): C0 + C1 = cin <= GM_GN_TABLE_MAX_CHANNELS in whole groups, rows = n_samples *
+ *                         rows_per_sample, rows_per_sample a multiple of 64, cin a multiple of the MFMA K step (32 bf16 / 16 fp32), cout > 16
+ *   vt (NULL: none)       the call is the stacked q | k | v projection of an attention block (diffusion_model_unet.py:407-415): its V columns (channels >= vt_c0,
+ *                         whole heads of vt_dh channels) are also stored as the V^T image of the LDS-DMA attention kernel at the head of its workspace (GmAttnDesc.
+ *                         vt_packed = 1 then skips the pack launch); bf16, rows_per_sample = tokens per sample, a multiple of 64 dividing rows, no residual, post_act 0 */
+typedef struct GmRowsDesc {
+  const void* x; long long x_ld;
+  const void* w; const float* bias;
+  const void* res; long long res_ld;
+  void* y; long long y_ld;
+  int rows, cin, cout, pre_act, post_act, dtype;
+  const float* pre_scale; const float* pre_shift; long long ss_ld;
+  const GmGnTables* gn; int n_samples, rows_per_sample;
+  void* vt; int vt_c0, vt_dh;
+} GmRowsDesc;
+int gm_rows_gemm(const GmRowsDesc* d, void* stream);
+/* The kernel gm_rows_gemm launches for `d` (its launcher switches on this function), or a negative error where it refuses `d`: no device call, no operand
+ * read.  KSPLIT: at most 16 rows, a long K, no (scale, shift) tables -- the K chunks dealt to the four waves of a work-group.  WIDE: gn, or at least
+ * gm_token_gemm_set_wide's rows, cin a multiple of the MFMA K step, cout > 16 -- 16 rows x 32 .. 64 channels per wave.  ROWS: the rest -- 16 x 16 per wave. */
+#define GM_ROWS_ROUTE_ROWS 0
+#define GM_ROWS_ROUTE_KSPLIT 1
+#define GM_ROWS_ROUTE_WIDE 2
+int gm_rows_gemm_route(const GmRowsDesc* d);
 
-/* One KV-cache decoding step of the decoder-only transformer issued natively (38-62 launches back to back, by how many of the fused kernels of small_ops.hip take the geometry): embed the fed token at
+/* One KV-cache decoding step of the decoder-only transformer issued natively (38-62 launches back to back, by how many of the fused kernels of rows_gemm.hip / decode_attention.hip take the geometry): embed the fed token at
  * `pos`, per block LayerNorm -> q|k|v -> append k, v to the caches -> 1 x (pos+1) attention -> out_proj + x -> LayerNorm -> MLP(GELU) + x,
  * then to_logits (networks/nets/transformer.py:98-106, blocks/transformerblock.py:86-91, blocks/selfattention.py:98-147; no cross
  * attention).  Weights are gm_pack_conv_weight images of the nn.Linear matrices (q, k, v stacked along the output dim). */

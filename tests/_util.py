@@ -42,7 +42,9 @@ HOST_PLANNERS = {"gm_conv_cfg_tile", "gm_conv_lds_bytes", "gm_conv_stats_slots",
                  # ... and the attention planners (tests/test_attention_routes.py): pure arithmetic on a descriptor
                  "gm_attention_backward_workspace_bytes", "gm_attention_backward_fused_workspace_bytes", "gm_attention_bwd_scores_workspace_bytes",
                  "gm_attention_workspace_bytes", "gm_attention_stats_slots", "gm_attention_max_head_dim", "gm_attention_max_wide_head_dim",
-                 "gm_conv_wgrad_workspace_bytes"}
+                 "gm_conv_wgrad_workspace_bytes",
+                 # ... and the route of the row GEMMs (tests/test_rows_routes.py)
+                 "gm_rows_gemm_route"}
 
 
 class _Pointer(int):
@@ -52,7 +54,8 @@ class _Pointer(int):
 class RecordingLibrary:
     """Stands in for the native library: the host-side planners go through to it, every other entry point is NOT called -- the call is
     appended to `calls` as [name, argument, ...] and 0 returned.  A pointer argument is recorded as null / non-null, an integer or float as
-    itself, a structure passed by reference as the list of its fields in declaration order (pointers again as booleans).
+    itself, a structure passed by reference as the list of its fields in declaration order (pointers again as booleans; a field that points at
+    another structure as false or that structure's field list).
     Two options, both off by default:  `bases` = {name: tensor} -- a pointer into the storage of one of these tensors is recorded as
     [name, byte offset from the tensor's first element] (the first match in registration order; any other non-null pointer stays `true`) once
     named() has run;  `planner_returns` = {planner name: value} -- that host-side planner answers `value` instead of being asked."""
@@ -64,6 +67,8 @@ class RecordingLibrary:
         import ctypes as C
         if ctype is C.c_void_p:
             return bool(v) if self.bases is None else _Pointer(v or 0)
+        if isinstance(ctype, type) and issubclass(ctype, C._Pointer) and issubclass(ctype._type_, C.Structure):  # GmRowsDesc.gn: false, or the fields it points at
+            return [self._value(getattr(v.contents, f), t) for f, t in ctype._type_._fields_] if v else False
         if isinstance(ctype, type) and issubclass(ctype, C.Array):
             return [self._value(e, ctype._type_) for e in v]
         if isinstance(v, float):

@@ -192,12 +192,12 @@ def test_library_builds_and_exports_every_declared_symbol():
 def test_ctypes_prototypes_cover_the_header():
     assert sorted(_native.PROTOTYPES.keys()) == _header_functions()
     lib = _native.lib()
-    assert lib.gm_abi_version() == 1
+    assert lib.gm_abi_version() == 2
 
 
 def test_struct_layouts_match_the_compiled_header(compiled_layout):
     structs, classes = _header_structs(), _native_classes()
-    assert len(structs) == 11 and set(structs) == set(classes) == set(compiled_layout)  # nothing left out, on either side
+    assert len(structs) == 12 and set(structs) == set(classes) == set(compiled_layout)  # nothing left out, on either side
     assert all(len(compiled_layout[n][1]) == len(structs[n]) > 0 for n in structs)
     assert _layout_problems(compiled_layout, classes) == []
     assert _field_type_problems(structs, classes) == []
@@ -225,6 +225,8 @@ def test_the_checkers_report_a_doctored_prototype_and_a_doctored_field(compiled_
     bad = _layout_problems(compiled_layout, wide)
     assert bad and all(b.startswith("GmGnTables") for b in bad) and any(b.startswith("GmGnTables.eps:") for b in bad)
     same_size = dict(classes, GmGnTables=with_field(_native.GmGnTables, "eps", ctypes.c_int))  # same layout, wrong type: the type check's to find
+    # (GmRowsDesc.gn points at GmGnTables: the doctored set stays consistent, so that the one doctored field is the one report)
+    same_size["GmRowsDesc"] = with_field(_native.GmRowsDesc, "gn", ctypes.POINTER(same_size["GmGnTables"]))
     assert _layout_problems(compiled_layout, same_size) == []
     assert _field_type_problems(_header_structs(), same_size) == ["GmGnTables.eps: %s for float" % ctypes.c_int]
     short = dict(classes, GmConvDesc=with_field(_native.GmConvDesc, "pre_S", ctypes.c_int * 3))

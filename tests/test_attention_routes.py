@@ -310,7 +310,8 @@ def _census(write=None, parent=None):
 def test_attention_launches_match_the_table_recorded_before_the_backward_was_unified():
     """The attention entry points driven on CPU tensors over the case matrix above, every launching entry point of the library replaced by a
     recorder: for every case the same native calls in the same order with the same descriptors, operand offsets and refusals as
-    tests/golden/attention_routes.json.gz, which was recorded with this harness at the parent commit of the refactor (named in the file)."""
+    tests/golden/attention_routes.json.gz, which was recorded with this harness at the parent commit of the refactor (named in the file);
+    its gm_linear_rows* rows were since rewritten, argument by argument, as the gm_rows_gemm(GmRowsDesc) rows that replaced those entry points."""
     with gzip.open(os.path.join(GOLDEN, "attention_routes.json.gz"), "rt") as fh:
         want = json.load(fh)["cases"]
     got = json.loads(json.dumps(_census()))

@@ -38,7 +38,7 @@ def _p(split, ng, um, inp, merge, entry, mlp, kq, ko, ku, kd, kl):
     return dict(zip(SHORT, (split, ng, um, inp, merge, entry, mlp, kq, ko, ku, kd, kl)))
 
 
-# The expected plan of every entry with a HOST position, derived by hand from the predicates of csrc/small_ops.hip and csrc/decode_step.hip:
+# The expected plan of every entry with a HOST position, derived by hand from the predicates of csrc/rows_gemm.hip, csrc/decode_attention.hip and csrc/decode_step.hip:
 #   K-split GEMM: rows <= 16 and ceil(cin / BK) >= 8 (BK 16 fp32, 32 bf16);  fused MLP: K-split at C, C <= 512, M % 64 == 0;
 #   fused q|k|v: window > 256, dh % 16 == 0, C % BK == 0, (NG, UM) = (3 dh / 16, ceil(C / BK / 4)) rounded up into {(6,2), (6,4), (12,2)};
 #   partial merge in the out-projection: dh % VECW == 0 (VECW 4 fp32, 8 bf16) and the out-projection K-split.

@@ -51,7 +51,7 @@ def _check(got, want, dtype, what, extra=1.0):
 # ---------------------------------------------------------------------------------------------------------------------
 def test_library_loads_on_gpu():
     from generativemodels_amd import _native
-    assert _native.lib().gm_abi_version() == 1
+    assert _native.lib().gm_abi_version() == 2
     assert torch.cuda.is_available()
 
 
@@ -925,7 +925,7 @@ def test_attention_lds_dma_kernel(case, variant):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("rows,cin,cout", [(1, 256, 768), (5, 64, 257), (17, 1024, 256), (64, 40, 24)])
 def test_small_row_linear_kernel(rows, cin, cout, dtype):
-    """gm_linear_rows (small_ops.hip): the barrier-free GEMM that ops.linear / ops.conv(kernel=1) route to for <= 64 rows -- SiLU
+    """gm_rows_gemm (rows_gemm.hip): the barrier-free GEMM that ops.linear / ops.conv(kernel=1) route to for <= 64 rows -- SiLU
     prologue, bias, GELU epilogue, residual, ragged channel counts."""
     ops = _ops()
     x = _rand((rows, cin), 191).to(dtype)
@@ -968,7 +968,7 @@ def test_small_row_linear_reads_stay_inside_a_narrow_operand(dtype):
                          ids=lambda c: f"B{c[0]}H{c[1]}k{c[2]}d{c[3]}")
 def test_single_query_attention_over_a_kv_cache(case, dtype):
     """One query per (batch, head) over the first Lk rows of a longer per-sample cache (batch stride != Lk * C): the decode kernel of
-    small_ops.hip behind gm_attention_forward."""
+    decode_attention.hip behind gm_attention_forward."""
     ops = _ops()
     b, h, lk, dh = case
     c = h * dh
@@ -1253,7 +1253,7 @@ def test_conv_single_output_channel_marching_kernel(cin, sp, pro, dtype):
     (1, 1000, 64, 72, False, "none", True, True),      # no prologue, output channels not a multiple of 16, ConvTranspose weight layout
 ])
 def test_token_gemm_path_of_1x1_convolutions(n, tokens, cin, cout, pre, pre_act, res, transposed, dtype):
-    """gm_linear_rows_affine behind ops.conv(kernel=1) for a few thousand token rows: per-sample GroupNorm affine + activation prologue, bias,
+    """gm_rows_gemm with (scale, shift) tables behind ops.conv(kernel=1) for a few thousand token rows: per-sample GroupNorm affine + activation prologue, bias,
     residual -- against the same product in fp64, and against the tiled kernel it replaces there (reference op: diffusion_model_unet.py:395-405)."""
     ops = _ops()
     x = _rand((n, tokens, cin), 801).to(dtype)
@@ -1388,7 +1388,7 @@ def test_attention_merge_kernel_writes_the_output_statistics(case):
 @pytest.mark.parametrize("case", [(16, 1024, 64, 1, 32, 5), (1, 4096, 128, 1, 32, 16), (2, 512, 256, 4, 32, 128), (3, 320, 96, 1, 8, 3), (1, 192, 384, 8, 32, 100)],
                          ids=lambda c: f"B{c[0]}-L{c[1]}-C{c[2]}-H{c[3]}-S{c[5]}")
 def test_qkv_projection_finalises_its_groupnorm_from_the_statistic_tables(case, dtype):
-    """(round 6) gm_linear_rows_gn: the stacked q | k | v projection of an attention block takes the block's GroupNorm as a GnRecipe -- the statistic tables of the
+    """(round 6) gm_rows_gemm with GmRowsDesc.gn: the stacked q | k | v projection of an attention block takes the block's GroupNorm as a GnRecipe -- the statistic tables of the
     producer -- and finalises it in the wide token GEMM's prologue (no finalisation launch), storing the V^T image of the attention kernel from its epilogue.
     Against the SAME kernel fed with the finalisation launch's (scale, shift): BIT FOR BIT, V^T bytes and attention result included; against fp64 GroupNorm + Linear;
     tables of 3 ... 128 rows, several samples and heads, token counts that are multiples of 64 only.  Reference: AttentionBlock.forward, diffusion_model_unet.py:424-458."""
@@ -1438,7 +1438,7 @@ def test_qkv_projection_finalises_its_groupnorm_from_the_statistic_tables(case, 
 @pytest.mark.parametrize("case", [(1, 512, 256, 1), (1, 4096, 128, 1), (2, 256, 128, 2), (1, 640, 256, 4)], ids=lambda c: f"B{c[0]}-L{c[1]}-C{c[2]}-H{c[3]}")
 def test_qkv_projection_stores_the_transposed_v_image(case):
     """The stacked q | k | v projection of an attention block (small-row GEMM, GroupNorm affine as its prologue) can store the transposed,
-    key-permuted V image of the LDS-DMA attention kernel itself (gm_linear_rows_affine_vt -> GmAttnDesc.vt_packed): the attention result must be
+    key-permuted V image of the LDS-DMA attention kernel itself (GmRowsDesc.vt -> GmAttnDesc.vt_packed): the attention result must be
     bit-identical to the path with the separate pack launch, for several heads and batch entries."""
     ops = _ops()
     b, l, c, heads = case

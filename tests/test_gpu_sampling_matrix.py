@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the sampling-head kernels of csrc/transformer_ops.hip and the categorical draw of csrc/small_ops.hip over the sizes at which
+"""GPU (-m gpu): the sampling-head kernels and the categorical draw of csrc/transformer_ops.hip over the sizes at which
 a one-wave-per-row kernel can go wrong: vocabularies below, at and above one 64-lane pass (1, 63, 64, 65), several passes (257) and many
 (4097); rows that are views of a wider poisoned buffer; ties 64 entries apart (the same lane in two passes) and across +0 / -0.
 

@@ -1316,7 +1316,8 @@ def _conv_route_census(write=None, parent=None):
 def test_conv_routes_match_the_table_recorded_before_the_split_into_planner_and_launchers():
     """ops.conv / ops.linear driven on CPU tensors over the case matrix above, every launching entry point of the library replaced by a recorder
     (_util.conv_on_cpu): for every case the same entry points in the same order with the same arguments and descriptors as
-    tests/golden/conv_routes.json.gz, which was recorded with this harness at the parent commit of the refactor (named in the file)."""
+    tests/golden/conv_routes.json.gz, which was recorded with this harness at the parent commit of the refactor (named in the file);
+    its gm_linear_rows* rows were since rewritten, argument by argument, as the gm_rows_gemm(GmRowsDesc) rows that replaced those entry points."""
     import gzip
     import json
     import os

@@ -173,7 +173,7 @@ def test_the_ctypes_descriptor_follows_the_header_field_order():
 
 
 # ---- the launch sequence ---------------------------------------------------------------------------------------------------------------------
-_GEMMS = ("gm_conv_forward", "gm_linear_rows", "gm_linear_rows_affine", "gm_linear_rows_affine_vt", "gm_linear_rows_gn")
+_GEMMS = ("gm_conv_forward", "gm_rows_gemm")
 _DESC = 7  # position of the GmResizeDesc in a recorded gm_resize_taps call: [name, x, x_ld, y, y_ld, N, C, desc, dtype, stream]
 
 

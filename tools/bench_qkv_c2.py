@@ -1,5 +1,5 @@
 """GPU: the q | k | v projection of C2's mid-block attention (32 768 tokens, 256 -> 768 channels, GroupNorm prologue): the tile kernels (cfg 9 is what
-the policy picks) vs the token GEMM (gm_linear_rows_affine) beyond its measured bounds.   usage: python tools/bench_qkv_c2.py"""
+the policy picks) vs the token GEMM (gm_rows_gemm) beyond its measured bounds.   usage: python tools/bench_qkv_c2.py"""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
