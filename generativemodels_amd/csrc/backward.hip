@@ -515,11 +515,8 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const T* __restrict__
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const long long rr = r + (long long)u * R < row_end ? r + (long long)u * R : r;
-        if constexpr (VEC == 1) { xv[u][0] = ElemIO<T>::ld(xb + rr * x_ld); gv[u][0] = ElemIO<T>::ld(gb + rr * gy_ld); }
-        else {
-          Vec16<T>::unpack(*reinterpret_cast<const uint4*>(xb + rr * x_ld), xv[u]);
-          Vec16<T>::unpack(*reinterpret_cast<const uint4*>(gb + rr * gy_ld), gv[u]);
-        }
+        VecIO<T, VEC>::ld(xb + rr * x_ld, xv[u]);
+        VecIO<T, VEC>::ld(gb + rr * gy_ld, gv[u]);
       }
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
@@ -567,17 +564,6 @@ extern "C" long long gm_gn_bwd_stats_slots(int N, long long V) {
   return nblk;
 }
 
-template <typename T, int VEC>
-static void launch_gn_bwd_stats(const void* x, long long x_ld, const void* gy, long long gy_ld, const float* scale, const float* shift,
-                                long long ss_ld, int N, long long V, int C, int act, double* out, hipStream_t st) {
-  const int CV = C / VEC, R = 256 / CV;
-  long long nblk; int rpb;
-  gn_bwd_stats_geometry(N, V, nblk, rpb);
-  dim3 grid((unsigned)nblk, N);
-  const size_t smem = (size_t)R * C * 2 * sizeof(float);
-  gn_bwd_stats_kernel<T, VEC><<<grid, 256, smem, st>>>((const T*)x, x_ld, (const T*)gy, gy_ld, scale, shift, ss_ld, V, C, act, rpb, out);
-}
-
 extern "C" int gm_gn_bwd_stats(const void* x, long long x_ld, const void* gy, long long gy_ld, const float* scale, const float* shift,
                                long long ss_ld, int N, long long V, int C, int act, double* out, int dtype, void* stream) {
   GM_REQUIRE(x && gy && scale && shift && out, "null pointer");
@@ -585,17 +571,17 @@ extern "C" int gm_gn_bwd_stats(const void* x, long long x_ld, const void* gy, lo
   if (N == 0 || V == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == GM_F32 ? 4 : 8;
-  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (gy_ld % vec == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)gy & 15) == 0);
-  GM_REQUIRE((vec_ok ? C / vec : C) <= 256, "too many channels for gm_gn_bwd_stats");
-  if (dtype == GM_F32) {
-    if (vec_ok) launch_gn_bwd_stats<float, 4>(x, x_ld, gy, gy_ld, scale, shift, ss_ld, N, V, C, act, out, st);
-    else launch_gn_bwd_stats<float, 1>(x, x_ld, gy, gy_ld, scale, shift, ss_ld, N, V, C, act, out, st);
-  } else if (dtype == GM_BF16) {
-    if (vec_ok) launch_gn_bwd_stats<bf16_raw, 8>(x, x_ld, gy, gy_ld, scale, shift, ss_ld, N, V, C, act, out, st);
-    else launch_gn_bwd_stats<bf16_raw, 1>(x, x_ld, gy, gy_ld, scale, shift, ss_ld, N, V, C, act, out, st);
-  } else {
-    GM_FAIL(-2, "unsupported dtype");
-  }
+  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (gy_ld % vec == 0) && gm_aligned16(x) && gm_aligned16(gy);
+  const int CV = vec_ok ? C / vec : C;
+  GM_REQUIRE(CV <= 256, "too many channels for gm_gn_bwd_stats");
+  long long nblk; int rpb;
+  gn_bwd_stats_geometry(N, V, nblk, rpb);
+  dim3 grid((unsigned)nblk, N);
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        const size_t smem = (size_t)(256 / CV) * C * 2 * sizeof(float);  // [R][C] partial sums of g and of g * x
+        gn_bwd_stats_kernel<T, decltype(tv)::vec><<<grid, 256, smem, st>>>((const T*)x, x_ld, (const T*)gy, gy_ld, scale, shift, ss_ld, V, C, act, rpb, out);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -695,11 +681,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
       const long long rr = r + (long long)u * R < row_end ? r + (long long)u * R : r;
-      if constexpr (VEC == 1) { xv[u][0] = ElemIO<T>::ld(xb + rr * x_ld); gv[u][0] = ElemIO<T>::ld(gb + rr * gy_ld); }
-      else {
-        Vec16<T>::unpack(*reinterpret_cast<const uint4*>(xb + rr * x_ld), xv[u]);
-        Vec16<T>::unpack(*reinterpret_cast<const uint4*>(gb + rr * gy_ld), gv[u]);
-      }
+      VecIO<T, VEC>::ld(xb + rr * x_ld, xv[u]);
+      VecIO<T, VEC>::ld(gb + rr * gy_ld, gv[u]);
     }
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
@@ -729,8 +712,7 @@ extern "C" int gm_gn_bwd_apply(const void* x, long long x_ld, const void* gy, lo
   if ((long long)N * V * C == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == GM_F32 ? 4 : 8;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (gy_ld % vec == 0) && (dx_ld % vec == 0) && al(x) && al(gy) && al(dx);
+  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (gy_ld % vec == 0) && (dx_ld % vec == 0) && gm_aligned16(x) && gm_aligned16(gy) && gm_aligned16(dx);
   const int CV = vec_ok ? C / vec : C;
   GM_REQUIRE(CV <= 256, "too many channels for gm_gn_bwd_apply");
   const int R = 256 / CV;
@@ -740,12 +722,11 @@ extern "C" int gm_gn_bwd_apply(const void* x, long long x_ld, const void* gy, lo
   const int rpb = (int)((V + nblk - 1) / nblk);
   nblk = (V + rpb - 1) / rpb;
   dim3 grid((unsigned)nblk, N);
-#define GM_GNB_LAUNCH(T, VEC) \
-  gn_bwd_apply_kernel<T, VEC><<<grid, 256, 0, st>>>((const T*)x, x_ld, (const T*)gy, gy_ld, (T*)dx, dx_ld, scale, shift, ss_ld, A, B, Cc, V, C, rpb, act)
-  if (dtype == GM_F32) { if (vec_ok) GM_GNB_LAUNCH(float, 4); else GM_GNB_LAUNCH(float, 1); }
-  else if (dtype == GM_BF16) { if (vec_ok) GM_GNB_LAUNCH(bf16_raw, 8); else GM_GNB_LAUNCH(bf16_raw, 1); }
-  else GM_FAIL(-2, "unsupported dtype");
-#undef GM_GNB_LAUNCH
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        gn_bwd_apply_kernel<T, decltype(tv)::vec><<<grid, 256, 0, st>>>((const T*)x, x_ld, (const T*)gy, gy_ld, (T*)dx, dx_ld, scale, shift, ss_ld, A, B, Cc, V,
+                                                                      C, rpb, act);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -776,13 +757,11 @@ extern "C" int gm_spade_bwd(const void* xn, long long x_ld, const void* g, const
   long long grid = (total + 255) / 256;
   if (grid > 256 * 16) grid = 256 * 16;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    spade_bwd_kernel<float><<<(int)grid, 256, 0, st>>>((const float*)xn, x_ld, (const float*)g, (const float*)bm, gb_ld, (const float*)gy, gy_ld,
-                                                       (float*)dxn, dx_ld, (float*)dg, (float*)dbm, dgb_ld, C, total, act);
-  else if (dtype == GM_BF16)
-    spade_bwd_kernel<bf16_raw><<<(int)grid, 256, 0, st>>>((const bf16_raw*)xn, x_ld, (const bf16_raw*)g, (const bf16_raw*)bm, gb_ld, (const bf16_raw*)gy,
-                                                          gy_ld, (bf16_raw*)dxn, dx_ld, (bf16_raw*)dg, (bf16_raw*)dbm, dgb_ld, C, total, act);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        spade_bwd_kernel<T><<<(int)grid, 256, 0, st>>>((const T*)xn, x_ld, (const T*)g, (const T*)bm, gb_ld, (const T*)gy, gy_ld, (T*)dxn, dx_ld, (T*)dg,
+                                                       (T*)dbm, dgb_ld, C, total, act);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -910,13 +889,10 @@ extern "C" int gm_layernorm_bwd(const void* x, long long x_ld, const void* gy, l
       attr_set = true;
     }
   }
-  if (dtype == GM_F32)
-    layernorm_bwd_kernel<float><<<grid, 256, smem, st>>>((const float*)x, x_ld, (const float*)gy, gy_ld, (float*)dx, dx_ld, gamma, rows, C, eps, param_stats);
-  else if (dtype == GM_BF16)
-    layernorm_bwd_kernel<bf16_raw><<<grid, 256, smem, st>>>((const bf16_raw*)x, x_ld, (const bf16_raw*)gy, gy_ld, (bf16_raw*)dx, dx_ld, gamma, rows, C,
-                                                            eps, param_stats);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        layernorm_bwd_kernel<T><<<grid, 256, smem, st>>>((const T*)x, x_ld, (const T*)gy, gy_ld, (T*)dx, dx_ld, gamma, rows, C, eps, param_stats);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -945,9 +921,9 @@ extern "C" int gm_geglu_bwd(const void* x, long long x_ld, const void* gy, long 
   long long g = (total + 255) / 256;
   if (g > 8192) g = 8192;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32) geglu_bwd_kernel<float><<<(int)g, 256, 0, st>>>((const float*)x, x_ld, (const float*)gy, gy_ld, (float*)dx, dx_ld, rows, inner);
-  else if (dtype == GM_BF16)
-    geglu_bwd_kernel<bf16_raw><<<(int)g, 256, 0, st>>>((const bf16_raw*)x, x_ld, (const bf16_raw*)gy, gy_ld, (bf16_raw*)dx, dx_ld, rows, inner);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        geglu_bwd_kernel<T><<<(int)g, 256, 0, st>>>((const T*)x, x_ld, (const T*)gy, gy_ld, (T*)dx, dx_ld, rows, inner);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }

@@ -3,7 +3,6 @@
 #include "gm_common.h"
 
 // ---- host predicates shared by the eligibility tests of the LDS-DMA kernels ---------------------------------------------------------------------------------
-static inline bool gm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // the statistics form of a GroupNorm prologue (GmConvDesc.pre_stats / GmGnTables): one or two 16-byte aligned sources of 1 .. GM_GN_SHORT_MAX_ROWS rows whose
 // channels add up to cin; no second source, no second channel count.  (Each consumer adds the bounds of its own LDS tables.)
 static inline bool gm_gn_stats_form_ok(const double* const stats[2], const int S[2], const int C[2], int cin) {
@@ -71,30 +70,6 @@ __device__ __forceinline__ float conv_post_act(float v, int act) {
     default: return v;
   }
 }
-
-// 16-byte operand vector <-> 4/8 floats
-template <typename T> struct Vec16;
-template <> struct Vec16<float> {
-  static __device__ __forceinline__ void unpack(const uint4& v, float* o) {
-    o[0] = __uint_as_float(v.x); o[1] = __uint_as_float(v.y); o[2] = __uint_as_float(v.z); o[3] = __uint_as_float(v.w);
-  }
-  static __device__ __forceinline__ uint4 pack(const float* o) {
-    return make_uint4(__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3]));
-  }
-};
-template <> struct Vec16<bf16_raw> {
-  static __device__ __forceinline__ void unpack(const uint4& v, float* o) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-  }
-  static __device__ __forceinline__ uint4 pack(const float* o) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(o[2 * i], o[2 * i + 1]);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
 
 template <typename T> struct Mma;
 template <> struct Mma<bf16_raw> {

@@ -96,16 +96,11 @@ extern "C" int gm_sched_step(const void* sample, const void* model_output, const
   const long long total = batch * inner;
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    sched_step_kernel<float, false><<<ew_grid(total), 256, 0, st>>>((const float*)sample, (const float*)model_output,
-                                                                    (const float*)noise, (float*)prev, (float*)x0, inner,
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        sched_step_kernel<T, false><<<ew_grid(total), 256, 0, st>>>((const T*)sample, (const T*)model_output, (const T*)noise, (T*)prev, (T*)x0, inner,
                                                                     mo_bstride, total, *p, nullptr, nullptr);
-  else if (dtype == GM_BF16)
-    sched_step_kernel<bf16_raw, false><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)sample, (const bf16_raw*)model_output,
-                                                                       (const bf16_raw*)noise, (bf16_raw*)prev, (bf16_raw*)x0,
-                                                                       inner, mo_bstride, total, *p, nullptr, nullptr);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -190,12 +185,10 @@ extern "C" int gm_lincomb(const void* const* x, const float* c, int k, float pos
   a.post_mul = post_mul;
   a.post_div = post_div;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    lincomb_kernel<float><<<ew_grid(n), 256, 0, st>>>(a, (float*)out, n);
-  else if (dtype == GM_BF16)
-    lincomb_kernel<bf16_raw><<<ew_grid(n), 256, 0, st>>>(a, (bf16_raw*)out, n);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        lincomb_kernel<T><<<ew_grid(n), 256, 0, st>>>(a, (T*)out, n);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -289,14 +282,10 @@ extern "C" int gm_likelihood_term(const void* x0, const void* xt, const void* mo
   const float cdf_c = sqrtf((float)(2.0 / 3.14159265358979323846));  // torch.sqrt(torch.Tensor([2.0 / math.pi]))
   const long long gx = likelihood_blocks(inner);
   dim3 grid((unsigned)gx, (unsigned)batch);
-  if (dtype == GM_F32)
-    likelihood_kl_kernel<float><<<grid, 256, 0, st>>>((const float*)x0, (const float*)xt, (const float*)model_output,
-                                                      (float*)kl, workspace, inner, mo_bstride, *p, cdf_c);
-  else if (dtype == GM_BF16)
-    likelihood_kl_kernel<bf16_raw><<<grid, 256, 0, st>>>((const bf16_raw*)x0, (const bf16_raw*)xt, (const bf16_raw*)model_output,
-                                                         (bf16_raw*)kl, workspace, inner, mo_bstride, *p, cdf_c);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        likelihood_kl_kernel<T><<<grid, 256, 0, st>>>((const T*)x0, (const T*)xt, (const T*)model_output, (T*)kl, workspace, inner, mo_bstride, *p, cdf_c);
+      })) GM_FAIL(-2, "unsupported dtype");
   likelihood_fold_kernel<<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(workspace, total, batch, (int)gx, 1.0 / (double)inner);
   GM_LAUNCH_CHECK();
 }
@@ -321,14 +310,17 @@ extern "C" int gm_axpby_rows(const void* x, const void* y, const float* a, const
   const long long total = batch * inner;
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    axpby_rows_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (const float*)y, a, b, (float*)out, inner, total);
-  else if (dtype == GM_BF16)
-    axpby_rows_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)x, (const bf16_raw*)y, a, b,
-                                                                (bf16_raw*)out, inner, total);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        axpby_rows_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)x, (const T*)y, a, b, (T*)out, inner, total);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
+}
+
+// (source type, destination type) of the converting copies below: gm_dispatch_dtype nested; served when both are
+template <typename F> static inline bool gm_dispatch_dtype2(int src_dtype, int dst_dtype, F&& f) {
+  bool dst_ok = false;
+  return gm_dispatch_dtype(src_dtype, [&](auto ts) { dst_ok = gm_dispatch_dtype(dst_dtype, [&](auto td) { f(ts, td); }); }) && dst_ok;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -368,22 +360,17 @@ extern "C" int gm_copy_channels(const void* src, long long src_ld, int src_dtype
   const int es = src_dtype == GM_F32 ? 4 : 2;
   if (src_dtype == dst_dtype) {
     const int vec = 16 / es;
-    if (C % vec == 0 && src_ld % vec == 0 && dst_ld % vec == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0) {
+    if (C % vec == 0 && src_ld % vec == 0 && dst_ld % vec == 0 && gm_aligned16(src) && gm_aligned16(dst)) {
       copy_channels_vec_kernel<<<ew_grid(total / vec), 256, 0, st>>>((const uint4*)src, src_ld / vec, (uint4*)dst,
                                                                      dst_ld / vec, rows, C / vec);
       GM_LAUNCH_CHECK();
     }
   }
-  if (src_dtype == GM_F32 && dst_dtype == GM_F32)
-    copy_channels_kernel<float, float><<<ew_grid(total), 256, 0, st>>>((const float*)src, src_ld, (float*)dst, dst_ld, rows, C);
-  else if (src_dtype == GM_F32 && dst_dtype == GM_BF16)
-    copy_channels_kernel<float, bf16_raw><<<ew_grid(total), 256, 0, st>>>((const float*)src, src_ld, (bf16_raw*)dst, dst_ld, rows, C);
-  else if (src_dtype == GM_BF16 && dst_dtype == GM_F32)
-    copy_channels_kernel<bf16_raw, float><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)src, src_ld, (float*)dst, dst_ld, rows, C);
-  else if (src_dtype == GM_BF16 && dst_dtype == GM_BF16)
-    copy_channels_kernel<bf16_raw, bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)src, src_ld, (bf16_raw*)dst, dst_ld, rows, C);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype2(src_dtype, dst_dtype, [&](auto ts, auto td) {
+        using TS = typename decltype(ts)::type;
+        using TD = typename decltype(td)::type;
+        copy_channels_kernel<TS, TD><<<ew_grid(total), 256, 0, st>>>((const TS*)src, src_ld, (TD*)dst, dst_ld, rows, C);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -433,29 +420,18 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const TS* __restrict_
   }
 }
 
-
-template <typename TS, typename TD>
-static void launch_nchw_to_nhwc(const void* src, void* dst, int N, int C, long long V, long long dst_ld, hipStream_t st) {
-  dim3 grid(gm_cdiv(V, 32), gm_cdiv(C, 32), N);
-  nchw_to_nhwc_kernel<TS, TD><<<grid, 256, 0, st>>>((const TS*)src, (TD*)dst, C, V, dst_ld);
-}
-template <typename TS, typename TD>
-static void launch_nhwc_to_nchw(const void* src, long long src_ld, void* dst, int N, int C, long long V, hipStream_t st) {
-  dim3 grid(gm_cdiv(V, 32), gm_cdiv(C, 32), N);
-  nhwc_to_nchw_kernel<TS, TD><<<grid, 256, 0, st>>>((const TS*)src, src_ld, (TD*)dst, C, V);
-}
-
 extern "C" int gm_nchw_to_nhwc(const void* src, int src_dtype, void* dst, int dst_dtype, int N, int C, long long V,
                                long long dst_ld, void* stream) {
   GM_REQUIRE(src && dst, "null pointer");
   if ((long long)N * C * V == 0) return 0;
   GM_REQUIRE(N <= 65535 && gm_cdiv(C, 32) <= 65535, "batch / channel count too large for the grid");
   hipStream_t st = (hipStream_t)stream;
-  if (src_dtype == GM_F32 && dst_dtype == GM_F32) launch_nchw_to_nhwc<float, float>(src, dst, N, C, V, dst_ld, st);
-  else if (src_dtype == GM_F32 && dst_dtype == GM_BF16) launch_nchw_to_nhwc<float, bf16_raw>(src, dst, N, C, V, dst_ld, st);
-  else if (src_dtype == GM_BF16 && dst_dtype == GM_F32) launch_nchw_to_nhwc<bf16_raw, float>(src, dst, N, C, V, dst_ld, st);
-  else if (src_dtype == GM_BF16 && dst_dtype == GM_BF16) launch_nchw_to_nhwc<bf16_raw, bf16_raw>(src, dst, N, C, V, dst_ld, st);
-  else GM_FAIL(-2, "unsupported dtype");
+  dim3 grid(gm_cdiv(V, 32), gm_cdiv(C, 32), N);
+  if (!gm_dispatch_dtype2(src_dtype, dst_dtype, [&](auto ts, auto td) {
+        using TS = typename decltype(ts)::type;
+        using TD = typename decltype(td)::type;
+        nchw_to_nhwc_kernel<TS, TD><<<grid, 256, 0, st>>>((const TS*)src, (TD*)dst, C, V, dst_ld);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -465,11 +441,12 @@ extern "C" int gm_nhwc_to_nchw(const void* src, long long src_ld, int src_dtype,
   if ((long long)N * C * V == 0) return 0;
   GM_REQUIRE(N <= 65535 && gm_cdiv(C, 32) <= 65535, "batch / channel count too large for the grid");
   hipStream_t st = (hipStream_t)stream;
-  if (src_dtype == GM_F32 && dst_dtype == GM_F32) launch_nhwc_to_nchw<float, float>(src, src_ld, dst, N, C, V, st);
-  else if (src_dtype == GM_F32 && dst_dtype == GM_BF16) launch_nhwc_to_nchw<float, bf16_raw>(src, src_ld, dst, N, C, V, st);
-  else if (src_dtype == GM_BF16 && dst_dtype == GM_F32) launch_nhwc_to_nchw<bf16_raw, float>(src, src_ld, dst, N, C, V, st);
-  else if (src_dtype == GM_BF16 && dst_dtype == GM_BF16) launch_nhwc_to_nchw<bf16_raw, bf16_raw>(src, src_ld, dst, N, C, V, st);
-  else GM_FAIL(-2, "unsupported dtype");
+  dim3 grid(gm_cdiv(V, 32), gm_cdiv(C, 32), N);
+  if (!gm_dispatch_dtype2(src_dtype, dst_dtype, [&](auto ts, auto td) {
+        using TS = typename decltype(ts)::type;
+        using TD = typename decltype(td)::type;
+        nhwc_to_nchw_kernel<TS, TD><<<grid, 256, 0, st>>>((const TS*)src, src_ld, (TD*)dst, C, V);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -521,11 +498,10 @@ extern "C" int gm_resample2x(const void* src, long long src_ld, void* dst, long 
   long long total = (long long)N * C * (mode == 0 ? (long long)Di * fd * Hi * 2 * Wi * 2 : (long long)(Di / fd) * (Hi / 2) * (Wi / 2));
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    resample2x_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)src, src_ld, (float*)dst, dst_ld, N, C, Di, Hi, Wi, act_d, mode);
-  else if (dtype == GM_BF16)
-    resample2x_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)src, src_ld, (bf16_raw*)dst, dst_ld, N, C, Di, Hi, Wi, act_d, mode);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        resample2x_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)src, src_ld, (T*)dst, dst_ld, N, C, Di, Hi, Wi, act_d, mode);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -560,11 +536,10 @@ extern "C" int gm_phase2x(const void* src, long long src_ld, void* dst, long lon
   const long long total = (long long)N * C * (act_d ? (Di - rd + 1) / 2 : Di) * ((Hi - rh + 1) / 2) * ((Wi - rw + 1) / 2);
   if (total <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    phase2x_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)src, src_ld, (float*)dst, dst_ld, N, C, Di, Hi, Wi, act_d, phase);
-  else if (dtype == GM_BF16)
-    phase2x_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)src, src_ld, (bf16_raw*)dst, dst_ld, N, C, Di, Hi, Wi, act_d, phase);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        phase2x_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)src, src_ld, (T*)dst, dst_ld, N, C, Di, Hi, Wi, act_d, phase);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -597,9 +572,10 @@ extern "C" int gm_timestep_embedding(const float* timesteps, void* out, int B, i
   if (B * dim == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int grid = gm_cdiv((long long)B * dim, 256);
-  if (dtype == GM_F32) timestep_embedding_kernel<float><<<grid, 256, 0, st>>>(timesteps, (float*)out, B, dim, max_period);
-  else if (dtype == GM_BF16) timestep_embedding_kernel<bf16_raw><<<grid, 256, 0, st>>>(timesteps, (bf16_raw*)out, B, dim, max_period);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        timestep_embedding_kernel<T><<<grid, 256, 0, st>>>(timesteps, (T*)out, B, dim, max_period);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -624,9 +600,10 @@ extern "C" int gm_geglu(const void* x, long long x_ld, void* out, long long out_
   const long long total = rows * inner;
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32) geglu_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, x_ld, (float*)out, out_ld, rows, inner);
-  else if (dtype == GM_BF16) geglu_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)x, x_ld, (bf16_raw*)out, out_ld, rows, inner);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        geglu_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)x, x_ld, (T*)out, out_ld, rows, inner);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -654,11 +631,10 @@ extern "C" int gm_aekl_sample(const void* mu, const void* logvar, const void* ep
   GM_REQUIRE(!z || (mu && eps), "z needs mu and eps");
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    aekl_sample_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)mu, (const float*)logvar, (const float*)eps, (float*)sigma, (float*)z, total);
-  else if (dtype == GM_BF16)
-    aekl_sample_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)mu, (const bf16_raw*)logvar, (const bf16_raw*)eps, (bf16_raw*)sigma, (bf16_raw*)z, total);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        aekl_sample_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)mu, (const T*)logvar, (const T*)eps, (T*)sigma, (T*)z, total);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -677,9 +653,10 @@ extern "C" int gm_addcmul(const void* a, const void* b, const void* c, void* out
   GM_REQUIRE(a && b && c && out, "null pointer");
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32) addcmul_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)a, (const float*)b, (const float*)c, (float*)out, total);
-  else if (dtype == GM_BF16) addcmul_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)a, (const bf16_raw*)b, (const bf16_raw*)c, (bf16_raw*)out, total);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        addcmul_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)a, (const T*)b, (const T*)c, (T*)out, total);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -697,9 +674,10 @@ extern "C" int gm_scale(const void* x, void* out, float s, int mode, long long t
   GM_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (multiply) or 1 (divide)");
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32) scale_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (float*)out, s, mode, total);
-  else if (dtype == GM_BF16) scale_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)x, (bf16_raw*)out, s, mode, total);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        scale_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)x, (T*)out, s, mode, total);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -746,9 +724,10 @@ extern "C" int gm_activation(const void* x, const void* g, void* out, int act, i
   GM_REQUIRE(act >= 0 && act <= 6, "unknown activation code");
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32) activation_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (const float*)g, (float*)out, act, mode, total);
-  else if (dtype == GM_BF16) activation_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)x, (const bf16_raw*)g, (bf16_raw*)out, act, mode, total);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        activation_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)x, (const T*)g, (T*)out, act, mode, total);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -784,11 +763,9 @@ extern "C" int gm_nearest_resize(const void* x, long long x_ld, void* y, long lo
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const float sd = (float)Di / (float)Do, sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
-  if (dtype == GM_F32)
-    nearest_resize_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, x_ld, (float*)y, y_ld, N, Di, Hi, Wi, Do, Ho, Wo, C, sd, sh, sw);
-  else if (dtype == GM_BF16)
-    nearest_resize_kernel<bf16_raw><<<ew_grid(total), 256, 0, st>>>((const bf16_raw*)x, x_ld, (bf16_raw*)y, y_ld, N, Di, Hi, Wi, Do, Ho, Wo, C, sd, sh, sw);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        nearest_resize_kernel<T><<<ew_grid(total), 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, N, Di, Hi, Wi, Do, Ho, Wo, C, sd, sh, sw);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }

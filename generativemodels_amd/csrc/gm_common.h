@@ -45,12 +45,76 @@ template <> struct ElemIO<bf16_raw> {
   static __device__ __forceinline__ float ld(const bf16_raw* p) { return bf16_to_f32(*p); }
   static __device__ __forceinline__ void st(bf16_raw* p, float v) { *p = f32_to_bf16(v); }
 };
+template <> struct ElemIO<_Float16> {  // (inputs of the metric kernels only: gm_dispatch_dtype_f16)
+  static __device__ __forceinline__ float ld(const _Float16* p) { return (float)*p; }
+  static __device__ __forceinline__ void st(_Float16* p, float v) { *p = (_Float16)v; }
+};
 
 // two fp32 -> packed bf16x2 (lo in bits 0..15) with the gfx950 hardware converter (round-to-nearest-even)
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   uint32_t r;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
   return r;
+}
+
+// 16-byte operand vector <-> 4/8 floats
+template <typename T> struct Vec16;
+template <> struct Vec16<float> {
+  static __device__ __forceinline__ void unpack(const uint4& v, float* o) {
+    o[0] = __uint_as_float(v.x); o[1] = __uint_as_float(v.y); o[2] = __uint_as_float(v.z); o[3] = __uint_as_float(v.w);
+  }
+  static __device__ __forceinline__ uint4 pack(const float* o) {
+    return make_uint4(__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3]));
+  }
+};
+template <> struct Vec16<bf16_raw> {
+  static __device__ __forceinline__ void unpack(const uint4& v, float* o) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+  }
+  static __device__ __forceinline__ uint4 pack(const float* o) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(o[2 * i], o[2 * i + 1]);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
+};
+
+// ---- the IO of the streaming (memory-bound) kernels: VEC consecutive elements <-> VEC floats.  VEC = 16 / sizeof(T) is one 16-byte access (the host
+// has checked the alignment of the base, the pitches and the channel count: gm_aligned16 and the entry point's vec_ok), VEC = 1 is ElemIO. -------------
+template <typename T, int VEC> struct VecIO {
+  static_assert(VEC * sizeof(T) == 16, "a vector access is 16 bytes: 4 fp32 or 8 bf16");
+  static __device__ __forceinline__ void ld(const T* p, float* o) { Vec16<T>::unpack(*reinterpret_cast<const uint4*>(p), o); }
+  static __device__ __forceinline__ void st(T* p, const float* v) { *reinterpret_cast<uint4*>(p) = Vec16<T>::pack(v); }
+};
+template <typename T> struct VecIO<T, 1> {
+  static __device__ __forceinline__ void ld(const T* p, float* o) { o[0] = ElemIO<T>::ld(p); }
+  static __device__ __forceinline__ void st(T* p, const float* v) { ElemIO<T>::st(p, v[0]); }
+};
+static inline bool gm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- host dispatch over the storage type of a streaming entry point.  `f` is a generic lambda that launches for the tag it is given
+// (`using T = typename decltype(tv)::type`, `decltype(tv)::vec`); the result says whether the dtype is served.  The refusal stays in the entry point's
+// own body -- `if (!gm_dispatch_dtype(dtype, [&](auto tv) {...})) GM_FAIL(-2, "unsupported dtype");` -- because GM_FAIL records __func__. ----------------
+template <typename T, int VEC = 1> struct GmTV { using type = T; static constexpr int vec = VEC; };
+template <typename F> static inline bool gm_dispatch_dtype(int dtype, F&& f) {
+  if (dtype == GM_F32) f(GmTV<float>{});
+  else if (dtype == GM_BF16) f(GmTV<bf16_raw>{});
+  else return false;
+  return true;
+}
+// the three metric entry points also read fp16
+template <typename F> static inline bool gm_dispatch_dtype_f16(int dtype, F&& f) {
+  if (dtype == GM_F16) { f(GmTV<_Float16>{}); return true; }
+  return gm_dispatch_dtype(dtype, f);
+}
+// (type, vector width): the 16-byte form where the entry point's vec_ok holds, else one element per access
+template <typename F> static inline bool gm_dispatch_vec(int dtype, bool vec_ok, F&& f) {
+  if (dtype == GM_F32) { if (vec_ok) f(GmTV<float, 4>{}); else f(GmTV<float, 1>{}); }
+  else if (dtype == GM_BF16) { if (vec_ok) f(GmTV<bf16_raw, 8>{}); else f(GmTV<bf16_raw, 1>{}); }
+  else return false;
+  return true;
 }
 // fast SiLU for the bf16 path: v_exp_f32 + v_rcp_f32 (about 1 ulp each; far below bf16 resolution)
 __device__ __forceinline__ float gm_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

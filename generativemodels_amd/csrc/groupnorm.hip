@@ -15,31 +15,6 @@
 #define GN_THREADS 256
 #define GN_ROWS_PER_THREAD 64
 
-template <typename T, int VEC> struct VecLd;
-template <> struct VecLd<float, 4> {
-  static __device__ __forceinline__ void ld(const float* p, float* o) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  }
-};
-template <> struct VecLd<float, 1> {
-  static __device__ __forceinline__ void ld(const float* p, float* o) { o[0] = *p; }
-};
-template <> struct VecLd<bf16_raw, 8> {
-  static __device__ __forceinline__ void ld(const bf16_raw* p, float* o) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o[2 * i] = __uint_as_float(w[i] << 16);
-      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-};
-template <> struct VecLd<bf16_raw, 1> {
-  static __device__ __forceinline__ void ld(const bf16_raw* p, float* o) { o[0] = bf16_to_f32(*p); }
-};
-
 // grid (nblk, N).  partial[(n*nblk + blk)*G + g] = {sum, sumsq} (fp64) over rows [blk*rpb, (blk+1)*rpb) of sample n.
 template <typename T, int VEC>
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restrict__ x, long long ld, long long V, int C,
@@ -73,7 +48,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const long long rr = r + (long long)u * R;
-        VecLd<T, VEC>::ld(base + (rr < row_end ? rr : r) * ld, v[u]);
+        VecIO<T, VEC>::ld(base + (rr < row_end ? rr : r) * ld, v[u]);
       }
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
@@ -195,20 +170,14 @@ extern "C" int gm_gn_scale_shift(const void* x, long long ld, int N, long long V
   if (N == 0 || V == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int vecmax = dtype == GM_F32 ? 4 : 8;
-  const bool vec_ok = (C % vecmax == 0) && (ld % vecmax == 0) && (((uintptr_t)x & 15) == 0);
+  const bool vec_ok = (C % vecmax == 0) && (ld % vecmax == 0) && gm_aligned16(x);
   const int CV = vec_ok ? C / vecmax : C;
   GM_REQUIRE(CV <= GN_THREADS, "too many channels for gm_gn_scale_shift");
   int nblk = 0;
   double2* ws = (double2*)workspace;
-  if (dtype == GM_F32) {
-    if (vec_ok) launch_gn_stats<float, 4>(x, ld, N, V, C, G, ws, &nblk, st);
-    else launch_gn_stats<float, 1>(x, ld, N, V, C, G, ws, &nblk, st);
-  } else if (dtype == GM_BF16) {
-    if (vec_ok) launch_gn_stats<bf16_raw, 8>(x, ld, N, V, C, G, ws, &nblk, st);
-    else launch_gn_stats<bf16_raw, 1>(x, ld, N, V, C, G, ws, &nblk, st);
-  } else {
-    GM_FAIL(-2, "unsupported dtype");
-  }
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        launch_gn_stats<typename decltype(tv)::type, decltype(tv)::vec>(x, ld, N, V, C, G, ws, &nblk, st);
+      })) GM_FAIL(-2, "unsupported dtype");
   {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) GM_FAIL((int)e, hipGetErrorString(e));
@@ -221,7 +190,7 @@ extern "C" int gm_gn_scale_shift(const void* x, long long ld, int N, long long V
 // the dispatcher picks, hence the pointer / pitch arguments).  -1: channel count not covered.
 extern "C" long long gm_gn_channel_stats_slots(const void* x, long long ld, long long V, int C, int dtype) {
   const int vecmax = dtype == GM_F32 ? 4 : 8;
-  const bool vec_ok = (C % vecmax == 0) && (ld % vecmax == 0) && (((uintptr_t)x & 15) == 0);
+  const bool vec_ok = (C % vecmax == 0) && (ld % vecmax == 0) && gm_aligned16(x);
   if ((vec_ok ? C / vecmax : C) > GN_THREADS) return -1;
   return V == 0 ? 1 : gn_nblk(V, C, vec_ok ? vecmax : 1);
 }
@@ -234,18 +203,12 @@ extern "C" int gm_gn_channel_stats(const void* x, long long ld, int N, long long
   if (N == 0 || V == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int vecmax = dtype == GM_F32 ? 4 : 8;
-  const bool vec_ok = (C % vecmax == 0) && (ld % vecmax == 0) && (((uintptr_t)x & 15) == 0);
+  const bool vec_ok = (C % vecmax == 0) && (ld % vecmax == 0) && gm_aligned16(x);
   GM_REQUIRE((vec_ok ? C / vecmax : C) <= GN_THREADS, "too many channels for gm_gn_channel_stats");
   int nblk = 0;
-  if (dtype == GM_F32) {
-    if (vec_ok) launch_gn_stats<float, 4>(x, ld, N, V, C, 1, nullptr, &nblk, st, chan_out);
-    else launch_gn_stats<float, 1>(x, ld, N, V, C, 1, nullptr, &nblk, st, chan_out);
-  } else if (dtype == GM_BF16) {
-    if (vec_ok) launch_gn_stats<bf16_raw, 8>(x, ld, N, V, C, 1, nullptr, &nblk, st, chan_out);
-    else launch_gn_stats<bf16_raw, 1>(x, ld, N, V, C, 1, nullptr, &nblk, st, chan_out);
-  } else {
-    GM_FAIL(-2, "unsupported dtype");
-  }
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        launch_gn_stats<typename decltype(tv)::type, decltype(tv)::vec>(x, ld, N, V, C, 1, nullptr, &nblk, st, chan_out);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -442,7 +405,7 @@ __global__ __launch_bounds__(256) void gn_apply_vec_kernel(const T* __restrict__
     const int c = (int)(i - row * CV) * VEC;
     const long long n = row / V;
     float v[VEC], sc[VEC], sh[VEC];
-    VecLd<T, VEC>::ld(x + row * x_ld + c, v);
+    VecIO<T, VEC>::ld(x + row * x_ld + c, v);
     // scale / shift as 16-byte vectors (c, ss_ld multiples of 4 floats: checked by the launcher), the activation chosen OUTSIDE the
     // element loop: a per-element `if (act == ...)` chain made hipcc split the loop into eight blocks with scalar loads in each
     // (measured: 1.6 TB/s instead of 4.9)
@@ -461,12 +424,7 @@ __global__ __launch_bounds__(256) void gn_apply_vec_kernel(const T* __restrict__
 #pragma unroll
       for (int k = 0; k < VEC; ++k) v[k] = fmaxf(v[k], 0.f);
     }
-    if (sizeof(T) == 4) {
-      *reinterpret_cast<float4*>(y + row * y_ld + c) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      *reinterpret_cast<uint4*>(y + row * y_ld + c) =
-          make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4 % VEC], v[5 % VEC]), pack_bf16x2(v[6 % VEC], v[7 % VEC]));
-    }
+    *reinterpret_cast<uint4*>(y + row * y_ld + c) = Vec16<T>::pack(v);  // (pack, then the address: VecIO::st takes the address first and hipcc schedules the bf16 packs differently)
   }
 }
 
@@ -501,7 +459,7 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const T* __restrict_
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
       const long long rr = r + (long long)u * R < row_end ? r + (long long)u * R : r;
-      VecLd<T, VEC>::ld(xb + rr * x_ld, v[u]);
+      VecIO<T, VEC>::ld(xb + rr * x_ld, v[u]);
     }
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
@@ -515,14 +473,7 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const T* __restrict_
         for (int k = 0; k < VEC; ++k) v[u][k] = fmaxf(v[u][k], 0.f);
       }
       const long long rr = r + (long long)u * R;
-      if (rr < row_end) {
-        if (sizeof(T) == 4) {
-          *reinterpret_cast<float4*>(yb + rr * y_ld) = make_float4(v[u][0], v[u][1], v[u][2], v[u][3]);
-        } else {
-          *reinterpret_cast<uint4*>(yb + rr * y_ld) = make_uint4(pack_bf16x2(v[u][0], v[u][1]), pack_bf16x2(v[u][2], v[u][3]),
-                                                                 pack_bf16x2(v[u][4 % VEC], v[u][5 % VEC]), pack_bf16x2(v[u][6 % VEC], v[u][7 % VEC]));
-        }
-      }
+      if (rr < row_end) *reinterpret_cast<uint4*>(yb + rr * y_ld) = Vec16<T>::pack(v[u]);
     }
   }
 }
@@ -535,40 +486,33 @@ extern "C" int gm_gn_apply(const void* x, long long x_ld, void* y, long long y_l
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == GM_F32 ? 4 : 8;
-  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (y_ld % vec == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) &&
-                      (ss_ld % 4 == 0) && (((uintptr_t)scale & 15) == 0) && (((uintptr_t)shift & 15) == 0);
+  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (y_ld % vec == 0) && gm_aligned16(x) && gm_aligned16(y) &&
+                      (ss_ld % 4 == 0) && gm_aligned16(scale) && gm_aligned16(shift);
   static const bool rows_form = !(getenv("GM_GN_APPLY_ROWS") && getenv("GM_GN_APPLY_ROWS")[0] == '0');  // bench switch (tools/layer_times.py)
-  if (rows_form && vec_ok && (dtype == GM_F32 || dtype == GM_BF16) && C / vec <= 256 && N <= 65535) {
-    const int R = 256 / (C / vec);
-    long long iters = (V + (long long)R * 2048 - 1) / ((long long)R * 2048);  // rows per lane: 4 .. 16, about 2048+ blocks per sample
-    iters = (iters + 3) / 4 * 4;
-    if (iters < 4) iters = 4;
-    if (iters > 16) iters = 16;
-    const int rpb = (int)(R * iters);
-    dim3 grid((unsigned)((V + rpb - 1) / rpb), (unsigned)N);
-    if (dtype == GM_F32)
-      gn_apply_rows_kernel<float, 4><<<grid, 256, 0, st>>>((const float*)x, x_ld, (float*)y, y_ld, scale, shift, ss_ld, V, C, rpb, act);
-    else
-      gn_apply_rows_kernel<bf16_raw, 8><<<grid, 256, 0, st>>>((const bf16_raw*)x, x_ld, (bf16_raw*)y, y_ld, scale, shift, ss_ld, V, C, rpb, act);
-    GM_LAUNCH_CHECK();
-  }
-  if (vec_ok && (dtype == GM_F32 || dtype == GM_BF16)) {
-    const long long tv = total / vec;
-    long long g = (tv + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;
-    if (dtype == GM_F32)
-      gn_apply_vec_kernel<float, 4><<<(int)g, 256, 0, st>>>((const float*)x, x_ld, (float*)y, y_ld, scale, shift, ss_ld, V, C, tv, act);
-    else
-      gn_apply_vec_kernel<bf16_raw, 8><<<(int)g, 256, 0, st>>>((const bf16_raw*)x, x_ld, (bf16_raw*)y, y_ld, scale, shift, ss_ld, V, C, tv, act);
-    GM_LAUNCH_CHECK();
-  }
-  long long g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (dtype == GM_F32)
-    gn_apply_kernel<float><<<(int)g, 256, 0, st>>>((const float*)x, x_ld, (float*)y, y_ld, scale, shift, ss_ld, V, C, total, act);
-  else if (dtype == GM_BF16)
-    gn_apply_kernel<bf16_raw><<<(int)g, 256, 0, st>>>((const bf16_raw*)x, x_ld, (bf16_raw*)y, y_ld, scale, shift, ss_ld, V, C, total, act);
-  else GM_FAIL(-2, "unsupported dtype");
+  // one of three kernels: the rows form, the grid-stride vector form (rows form switched off, C / vec > 256 or N > 65535), the scalar form
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        constexpr int VEC = decltype(tv)::vec;
+        if constexpr (VEC == 1) {
+          long long g = (total + 255) / 256;
+          if (g > 4096) g = 4096;
+          gn_apply_kernel<T><<<(int)g, 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, scale, shift, ss_ld, V, C, total, act);
+        } else if (rows_form && C / vec <= 256 && N <= 65535) {
+          const int R = 256 / (C / vec);
+          long long iters = (V + (long long)R * 2048 - 1) / ((long long)R * 2048);  // rows per lane: 4 .. 16, about 2048+ blocks per sample
+          iters = (iters + 3) / 4 * 4;
+          if (iters < 4) iters = 4;
+          if (iters > 16) iters = 16;
+          const int rpb = (int)(R * iters);
+          dim3 grid((unsigned)((V + rpb - 1) / rpb), (unsigned)N);
+          gn_apply_rows_kernel<T, VEC><<<grid, 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, scale, shift, ss_ld, V, C, rpb, act);
+        } else {
+          const long long tvec = total / vec;
+          long long g = (tvec + 255) / 256;
+          if (g > 256 * 16) g = 256 * 16;
+          gn_apply_vec_kernel<T, VEC><<<(int)g, 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, scale, shift, ss_ld, V, C, tvec, act);
+        }
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -586,9 +530,9 @@ __global__ __launch_bounds__(256) void spade_apply_kernel(const T* __restrict__ 
     const int c = (int)(i - row * CV) * VEC;
     const long long n = row / V;
     float v[VEC], gv[VEC], bv[VEC];
-    VecLd<T, VEC>::ld(x + row * x_ld + c, v);
-    VecLd<T, VEC>::ld(g + row * gb_ld + c, gv);
-    VecLd<T, VEC>::ld(bm + row * gb_ld + c, bv);
+    VecIO<T, VEC>::ld(x + row * x_ld + c, v);
+    VecIO<T, VEC>::ld(g + row * gb_ld + c, gv);
+    VecIO<T, VEC>::ld(bm + row * gb_ld + c, bv);
     const float* sc = scale + n * ss_ld + c;
     const float* sh = shift + n * ss_ld + c;
 #pragma unroll
@@ -609,18 +553,15 @@ extern "C" int gm_spade_apply(const void* x, long long x_ld, void* y, long long 
   if (total == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == GM_F32 ? 4 : 8;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (gb_ld % vec == 0) && al(x) && al(g) && al(bm);
+  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (gb_ld % vec == 0) && gm_aligned16(x) && gm_aligned16(g) && gm_aligned16(bm);
   const long long items = vec_ok ? total / vec : total;
   long long grid = (items + 255) / 256;
   if (grid > 256 * 16) grid = 256 * 16;
-#define GM_SPADE_LAUNCH(T, VEC)                                                                                                        \
-  spade_apply_kernel<T, VEC><<<(int)grid, 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, scale, shift, ss_ld, (const T*)g, (const T*)bm, gb_ld, V, C, \
-                                                     items, act)
-  if (dtype == GM_F32) { if (vec_ok) GM_SPADE_LAUNCH(float, 4); else GM_SPADE_LAUNCH(float, 1); }
-  else if (dtype == GM_BF16) { if (vec_ok) GM_SPADE_LAUNCH(bf16_raw, 8); else GM_SPADE_LAUNCH(bf16_raw, 1); }
-  else GM_FAIL(-2, "unsupported dtype");
-#undef GM_SPADE_LAUNCH
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        spade_apply_kernel<T, decltype(tv)::vec><<<(int)grid, 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, scale, shift, ss_ld, (const T*)g, (const T*)bm,
+                                                                          gb_ld, V, C, items, act);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -654,10 +595,9 @@ extern "C" int gm_layernorm(const void* x, long long x_ld, void* y, long long y_
   if (rows == 0 || C == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int grid = gm_cdiv(rows, 4);
-  if (dtype == GM_F32)
-    layernorm_kernel<float><<<grid, 256, 0, st>>>((const float*)x, x_ld, (float*)y, y_ld, gamma, beta, rows, C, eps);
-  else if (dtype == GM_BF16)
-    layernorm_kernel<bf16_raw><<<grid, 256, 0, st>>>((const bf16_raw*)x, x_ld, (bf16_raw*)y, y_ld, gamma, beta, rows, C, eps);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        layernorm_kernel<T><<<grid, 256, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, gamma, beta, rows, C, eps);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }

@@ -9,11 +9,6 @@
 #define SSIM_TH 16           // output tile (H, W) of a work-group; 256 threads, one output column each
 #define SSIM_TW 16
 
-template <typename T> struct MetricIn;
-template <> struct MetricIn<float> { static __device__ __forceinline__ float ld(const float* p) { return *p; } };
-template <> struct MetricIn<bf16_raw> { static __device__ __forceinline__ float ld(const bf16_raw* p) { return bf16_to_f32(*p); } };
-template <> struct MetricIn<_Float16> { static __device__ __forceinline__ float ld(const _Float16* p) { return (float)*p; } };
-
 struct SsimTaps { float d[SSIM_MAX_WINDOW], h[SSIM_MAX_WINDOW], w[SSIM_MAX_WINDOW]; };
 
 struct SsimGeom {
@@ -96,8 +91,8 @@ __global__ __launch_bounds__(256) void ssim_cs_kernel(const T* __restrict__ x, c
           float a = 0.0f, b = 0.0f;
           if (gh < g.H && gw < g.W) {
             const long long o = (long long)dz * plane + (long long)gh * g.W + gw;
-            a = MetricIn<T>::ld(xv + o);
-            b = MetricIn<T>::ld(yv + o);
+            a = ElemIO<T>::ld(xv + o);
+            b = ElemIO<T>::ld(yv + o);
           }
           rawx[r * RW + c] = a;
           rawy[r * RW + c] = b;
@@ -249,10 +244,11 @@ extern "C" int gm_ssim_cs(const void* x, const void* y, int dtype, long long B, 
   for (int j = 0; j < kh; ++j) taps.h[j] = taps_h[j];
   for (int j = 0; j < kw; ++j) taps.w[j] = taps_w[j];
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32) return ssim_launch<float>(x, y, B, C, g, c1, c2, taps, ssim_mean, cs_mean, ssim_map, cs_map, workspace, st);
-  if (dtype == GM_BF16) return ssim_launch<bf16_raw>(x, y, B, C, g, c1, c2, taps, ssim_mean, cs_mean, ssim_map, cs_map, workspace, st);
-  if (dtype == GM_F16) return ssim_launch<_Float16>(x, y, B, C, g, c1, c2, taps, ssim_mean, cs_mean, ssim_map, cs_map, workspace, st);
-  GM_FAIL(-2, "unsupported dtype");
+  int rc = 0;
+  if (!gm_dispatch_dtype_f16(dtype, [&](auto tv) {
+        rc = ssim_launch<typename decltype(tv)::type>(x, y, B, C, g, c1, c2, taps, ssim_mean, cs_mean, ssim_map, cs_map, workspace, st);
+      })) GM_FAIL(-2, "unsupported dtype");
+  return rc;
 }
 
 // ---- avg_pool{2,3}d(kernel_size=2) of two images at once: (nvol, D, H, W) -> (nvol, D / pd, H / 2, W / 2) fp32, pd = 2 (3-D) or 1 (2-D) ---------------------
@@ -271,8 +267,8 @@ __global__ __launch_bounds__(256) void avgpool2_pair_kernel(const T* __restrict_
     float sa = 0.0f, sb = 0.0f;
     for (int z = 0; z < pd; ++z) {
       const long long o = base + (long long)z * H * W;
-      sa += MetricIn<T>::ld(a + o) + MetricIn<T>::ld(a + o + 1) + MetricIn<T>::ld(a + o + W) + MetricIn<T>::ld(a + o + W + 1);
-      sb += MetricIn<T>::ld(b + o) + MetricIn<T>::ld(b + o + 1) + MetricIn<T>::ld(b + o + W) + MetricIn<T>::ld(b + o + W + 1);
+      sa += ElemIO<T>::ld(a + o) + ElemIO<T>::ld(a + o + 1) + ElemIO<T>::ld(a + o + W) + ElemIO<T>::ld(a + o + W + 1);
+      sb += ElemIO<T>::ld(b + o) + ElemIO<T>::ld(b + o + 1) + ElemIO<T>::ld(b + o + W) + ElemIO<T>::ld(b + o + W + 1);
     }
     oa[i] = sa * inv;
     ob[i] = sb * inv;
@@ -290,14 +286,10 @@ extern "C" int gm_avgpool2_pair(const void* a, const void* b, int dtype, float* 
   long long gx = (total + 255) / 256;
   if (gx > 65536) gx = 65536;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    avgpool2_pair_kernel<float><<<(unsigned)gx, 256, 0, st>>>((const float*)a, (const float*)b, out_a, out_b, total, D, H, W, Dp, Hp, Wp, pd);
-  else if (dtype == GM_BF16)
-    avgpool2_pair_kernel<bf16_raw><<<(unsigned)gx, 256, 0, st>>>((const bf16_raw*)a, (const bf16_raw*)b, out_a, out_b, total, D, H, W, Dp, Hp, Wp, pd);
-  else if (dtype == GM_F16)
-    avgpool2_pair_kernel<_Float16><<<(unsigned)gx, 256, 0, st>>>((const _Float16*)a, (const _Float16*)b, out_a, out_b, total, D, H, W, Dp, Hp, Wp, pd);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype_f16(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        avgpool2_pair_kernel<T><<<(unsigned)gx, 256, 0, st>>>((const T*)a, (const T*)b, out_a, out_b, total, D, H, W, Dp, Hp, Wp, pd);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -315,8 +307,8 @@ __global__ __launch_bounds__(256) void mmd_colsum_kernel(const T* __restrict__ y
   for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (long long)gridDim.x * blockDim.x) {
     double sy = 0.0, sp = 0.0;
     for (long long r = 0; r < B; ++r) {
-      sy += (double)MetricIn<T>::ld(y + r * F + f);
-      sp += (double)MetricIn<T>::ld(p + r * F + f);
+      sy += (double)ElemIO<T>::ld(y + r * F + f);
+      sp += (double)ElemIO<T>::ld(p + r * F + f);
     }
     yy += sy * sy;
     pp += sp * sp;
@@ -367,14 +359,10 @@ extern "C" int gm_mmd(const void* y, const void* y_pred, int dtype, long long B,
   GM_REQUIRE(workspace_bytes >= gx * (long long)sizeof(MmdPartial), "workspace too small (gm_mmd_workspace_bytes)");
   hipStream_t st = (hipStream_t)stream;
   MmdPartial* ws = (MmdPartial*)workspace;
-  if (dtype == GM_F32)
-    mmd_colsum_kernel<float><<<(unsigned)gx, 256, 0, st>>>((const float*)y, (const float*)y_pred, B, F, ws);
-  else if (dtype == GM_BF16)
-    mmd_colsum_kernel<bf16_raw><<<(unsigned)gx, 256, 0, st>>>((const bf16_raw*)y, (const bf16_raw*)y_pred, B, F, ws);
-  else if (dtype == GM_F16)
-    mmd_colsum_kernel<_Float16><<<(unsigned)gx, 256, 0, st>>>((const _Float16*)y, (const _Float16*)y_pred, B, F, ws);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype_f16(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        mmd_colsum_kernel<T><<<(unsigned)gx, 256, 0, st>>>((const T*)y, (const T*)y_pred, B, F, ws);
+      })) GM_FAIL(-2, "unsupported dtype");
   mmd_fold_kernel<<<1, 64, 0, st>>>(ws, (int)gx, 1.0 / ((double)B * (double)B * (double)F), out);
   GM_LAUNCH_CHECK();
 }

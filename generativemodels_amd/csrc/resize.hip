@@ -21,19 +21,7 @@ static int resize_grid(long long total, int per_block = 256) {
 template <typename T, int G, bool VEC>
 __device__ __forceinline__ void resize_load(const T* __restrict__ p, int cn, float (&v)[G]) {
   if constexpr (VEC) {
-    if constexpr (sizeof(T) == 4) {
-      const f32x4_t q = *reinterpret_cast<const f32x4_t*>(p);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = q[j];
-    } else {
-      const uint4 q = *reinterpret_cast<const uint4*>(p);
-      const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[2 * j] = __uint_as_float(u[j] << 16);
-        v[2 * j + 1] = __uint_as_float(u[j] & 0xffff0000u);
-      }
-    }
+    VecIO<T, G>::ld(p, v);
   } else {
 #pragma unroll
     for (int j = 0; j < G; ++j) v[j] = j < cn ? ElemIO<T>::ld(p + j) : 0.0f;
@@ -130,7 +118,7 @@ __global__ __launch_bounds__(256) void resize_taps_kernel(const T* __restrict__ 
 template <typename T>
 static void resize_launch(const void* x, long long x_ld, void* y, long long y_ld, int N, int C, const GmResizeDesc& d, hipStream_t st) {
   constexpr int GV = 16 / (int)sizeof(T);
-  const bool vec = C % GV == 0 && x_ld % GV == 0 && y_ld % GV == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;
+  const bool vec = C % GV == 0 && x_ld % GV == 0 && y_ld % GV == 0 && gm_aligned16(x) && gm_aligned16(y);
   const long long voxels = (long long)N * d.n_out[0] * d.n_out[1] * d.n_out[2];
   if (vec) {
     const int groups = C / GV;
@@ -148,12 +136,10 @@ extern "C" int gm_resize_taps(const void* x, long long x_ld, void* y, long long 
     GM_REQUIRE(d->n_in[a] > 0 && d->n_out[a] > 0, "empty spatial extent");
     GM_REQUIRE(d->start[a] && d->index[a] && d->weight[a], "null table");
   }
-  if (dtype != GM_F32 && dtype != GM_BF16) GM_FAIL(-2, "unsupported dtype");
-  if (N == 0 || C == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    resize_launch<float>(x, x_ld, y, y_ld, N, C, *d, st);
-  else
-    resize_launch<bf16_raw>(x, x_ld, y, y_ld, N, C, *d, st);
+  const bool empty = N == 0 || C == 0;  // (the dtype is refused before an empty problem returns)
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        if (!empty) resize_launch<typename decltype(tv)::type>(x, x_ld, y, y_ld, N, C, *d, (hipStream_t)stream);
+      })) GM_FAIL(-2, "unsupported dtype");
+  if (empty) return 0;
   GM_LAUNCH_CHECK();
 }

@@ -16,37 +16,6 @@
 #define GM_SB_ACT_SILU 1
 #define GM_SB_ACT_LEAKY 3  // (2 is ReLU in the shared activation table: LeakyReLU with slope 0)
 
-template <typename T, int VEC> struct SbIO;
-template <> struct SbIO<float, 4> {
-  static __device__ __forceinline__ void ld(const float* p, float* o) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  }
-  static __device__ __forceinline__ void st(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct SbIO<float, 1> {
-  static __device__ __forceinline__ void ld(const float* p, float* o) { o[0] = *p; }
-  static __device__ __forceinline__ void st(float* p, const float* v) { *p = v[0]; }
-};
-template <> struct SbIO<bf16_raw, 8> {
-  static __device__ __forceinline__ void ld(const bf16_raw* p, float* o) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o[2 * i] = __uint_as_float(w[i] << 16);
-      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void st(bf16_raw* p, const float* v) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
-  }
-};
-template <> struct SbIO<bf16_raw, 1> {
-  static __device__ __forceinline__ void ld(const bf16_raw* p, float* o) { o[0] = bf16_to_f32(*p); }
-  static __device__ __forceinline__ void st(bf16_raw* p, const float* v) { *p = f32_to_bf16(v[0]); }
-};
-
 template <typename T> __device__ __forceinline__ float sb_act(float v, int act, float slope) {
   if (act == GM_SB_ACT_SILU) return sizeof(T) == 4 ? gm_silu_precise(v) : gm_silu(v);
   if (act == GM_SB_ACT_LEAKY) return v > 0.f ? v : v * slope;
@@ -76,13 +45,13 @@ __global__ __launch_bounds__(256) void spade_block_apply_kernel(const T* __restr
     }
     const long long orow = n * Vo + v;
     float t[VEC], o[VEC];
-    SbIO<T, VEC>::ld(x + (n * Vs + sv) * x_ld + c, t);
+    VecIO<T, VEC>::ld(x + (n * Vs + sv) * x_ld + c, t);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) t[k] = t[k] * sc[c + k] + sh[c + k];
     if (g0) {
       float gv[VEC], bv[VEC];
-      SbIO<T, VEC>::ld(g0 + orow * gb0_ld + c, gv);
-      SbIO<T, VEC>::ld(b0 + orow * gb0_ld + c, bv);
+      VecIO<T, VEC>::ld(g0 + orow * gb0_ld + c, gv);
+      VecIO<T, VEC>::ld(b0 + orow * gb0_ld + c, bv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = t[k] * gv[k] + bv[k];
     } else {
@@ -93,14 +62,14 @@ __global__ __launch_bounds__(256) void spade_block_apply_kernel(const T* __restr
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = sb_act<T>(o[k], act0, slope);
     }
-    SbIO<T, VEC>::st(y0 + orow * y0_ld + c, o);
+    VecIO<T, VEC>::st(y0 + orow * y0_ld + c, o);
     if (g1) {
       float gv[VEC], bv[VEC];
-      SbIO<T, VEC>::ld(g1 + orow * gb1_ld + c, gv);
-      SbIO<T, VEC>::ld(b1 + orow * gb1_ld + c, bv);
+      VecIO<T, VEC>::ld(g1 + orow * gb1_ld + c, gv);
+      VecIO<T, VEC>::ld(b1 + orow * gb1_ld + c, bv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = t[k] * gv[k] + bv[k];
-      SbIO<T, VEC>::st(y1 + orow * y1_ld + c, o);
+      VecIO<T, VEC>::st(y1 + orow * y1_ld + c, o);
     }
   }
 }
@@ -123,24 +92,21 @@ extern "C" int gm_spade_block_apply(const void* x, long long x_ld, const float* 
   if ((long long)N * Vo * C == 0) return 0;
   GM_REQUIRE(N <= 65535, "batch above 65535");
   const int vec = dtype == GM_F32 ? 4 : 8;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (y0_ld % vec == 0) && al(x) && al(y0) &&
-                      (!g0 || ((gb0_ld % vec == 0) && al(g0) && al(b0))) &&
-                      (!g1 || ((gb1_ld % vec == 0) && (y1_ld % vec == 0) && al(g1) && al(b1) && al(y1)));
+  const bool vec_ok = (C % vec == 0) && (x_ld % vec == 0) && (y0_ld % vec == 0) && gm_aligned16(x) && gm_aligned16(y0) &&
+                      (!g0 || ((gb0_ld % vec == 0) && gm_aligned16(g0) && gm_aligned16(b0))) &&
+                      (!g1 || ((gb1_ld % vec == 0) && (y1_ld % vec == 0) && gm_aligned16(g1) && gm_aligned16(b1) && gm_aligned16(y1)));
   const long long CV = vec_ok ? C / vec : C, items = Vo * CV;
   GM_REQUIRE(items < (1ll << 32), "one sample holds 2^32 or more work items");
   long long grid = (items + 255) / 256;  // memory-bound: about 8 blocks per CU, the rest by grid stride
   const long long cap = (2048 + N - 1) / N;
   if (grid > cap) grid = cap;
   hipStream_t st = (hipStream_t)stream;
-#define GM_SB_LAUNCH(T, VEC)                                                                                                                       \
-  spade_block_apply_kernel<T, VEC><<<dim3((unsigned)grid, (unsigned)N), 256, 0, st>>>(                                                             \
-      (const T*)x, x_ld, scale, shift, ss_ld, (const T*)g0, (const T*)b0, gb0_ld, (T*)y0, y0_ld, (const T*)g1, (const T*)b1, gb1_ld, (T*)y1, y1_ld, \
-      (unsigned)Ho, (unsigned)Wo, (unsigned)Hs, (unsigned)Ws, Vs, Vo, (unsigned)CV, (unsigned)items, up, act0, slope)
-  if (dtype == GM_F32) { if (vec_ok) GM_SB_LAUNCH(float, 4); else GM_SB_LAUNCH(float, 1); }
-  else if (dtype == GM_BF16) { if (vec_ok) GM_SB_LAUNCH(bf16_raw, 8); else GM_SB_LAUNCH(bf16_raw, 1); }
-  else GM_FAIL(-2, "unsupported dtype");
-#undef GM_SB_LAUNCH
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        spade_block_apply_kernel<T, decltype(tv)::vec><<<dim3((unsigned)grid, (unsigned)N), 256, 0, st>>>(
+            (const T*)x, x_ld, scale, shift, ss_ld, (const T*)g0, (const T*)b0, gb0_ld, (T*)y0, y0_ld, (const T*)g1, (const T*)b1, gb1_ld, (T*)y1, y1_ld,
+            (unsigned)Ho, (unsigned)Wo, (unsigned)Hs, (unsigned)Ws, Vs, Vo, (unsigned)CV, (unsigned)items, up, act0, slope);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -150,17 +116,17 @@ __global__ __launch_bounds__(256) void leaky_relu_kernel(const T* __restrict__ x
                                                         long long items) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
     float v[VEC], o[VEC];
-    SbIO<T, VEC>::ld(x + i * VEC, v);
+    VecIO<T, VEC>::ld(x + i * VEC, v);
     if (gy) {
       float g[VEC];
-      SbIO<T, VEC>::ld(gy + i * VEC, g);
+      VecIO<T, VEC>::ld(gy + i * VEC, g);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = v[k] > 0.f ? g[k] : g[k] * slope;
     } else {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = v[k] > 0.f ? v[k] : v[k] * slope;
     }
-    SbIO<T, VEC>::st(out + i * VEC, o);
+    VecIO<T, VEC>::st(out + i * VEC, o);
   }
 }
 
@@ -169,17 +135,15 @@ extern "C" int gm_leaky_relu(const void* x, const void* gy, void* out, float slo
   GM_REQUIRE(total >= 0, "negative size");
   if (total == 0) return 0;
   const int vec = dtype == GM_F32 ? 4 : 8;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec_ok = (total % vec == 0) && al(x) && al(out) && (!gy || al(gy));
+  const bool vec_ok = (total % vec == 0) && gm_aligned16(x) && gm_aligned16(out) && (!gy || gm_aligned16(gy));
   const long long items = vec_ok ? total / vec : total;
   long long grid = (items + 255) / 256;
   if (grid > 2048) grid = 2048;
   hipStream_t st = (hipStream_t)stream;
-#define GM_LR_LAUNCH(T, VEC) leaky_relu_kernel<T, VEC><<<(unsigned)grid, 256, 0, st>>>((const T*)x, (const T*)gy, (T*)out, slope, items)
-  if (dtype == GM_F32) { if (vec_ok) GM_LR_LAUNCH(float, 4); else GM_LR_LAUNCH(float, 1); }
-  else if (dtype == GM_BF16) { if (vec_ok) GM_LR_LAUNCH(bf16_raw, 8); else GM_LR_LAUNCH(bf16_raw, 1); }
-  else GM_FAIL(-2, "unsupported dtype");
-#undef GM_LR_LAUNCH
+  if (!gm_dispatch_vec(dtype, vec_ok, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        leaky_relu_kernel<T, decltype(tv)::vec><<<(unsigned)grid, 256, 0, st>>>((const T*)x, (const T*)gy, (T*)out, slope, items);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -218,10 +182,9 @@ extern "C" int gm_kld(const void* mu, const void* logvar, long long total, float
   GM_REQUIRE((dmu == nullptr) == (dlogvar == nullptr), "the two gradients are written together");
   GM_REQUIRE(out || dmu, "nothing to write");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    kld_kernel<float><<<1, 256, 0, st>>>((const float*)mu, (const float*)logvar, total, out, upstream, (float*)dmu, (float*)dlogvar);
-  else if (dtype == GM_BF16)
-    kld_kernel<bf16_raw><<<1, 256, 0, st>>>((const bf16_raw*)mu, (const bf16_raw*)logvar, total, out, upstream, (bf16_raw*)dmu, (bf16_raw*)dlogvar);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        kld_kernel<T><<<1, 256, 0, st>>>((const T*)mu, (const T*)logvar, total, out, upstream, (T*)dmu, (T*)dlogvar);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }

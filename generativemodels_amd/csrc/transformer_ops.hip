@@ -39,14 +39,11 @@ extern "C" int gm_embed_tokens_dev(const long long* indices, const void* token_w
   hipStream_t st = (hipStream_t)stream;
   long long g = (rows * C + 255) / 256;
   if (g > 4096) g = 4096;
-  if (dtype == GM_F32)
-    embed_tokens_kernel<float><<<(int)g, 256, 0, st>>>(indices, (const float*)token_weight, (const float*)position_weight, (float*)out, rows,
-                                                       seq_len, C, pos0, num_tokens, max_positions, pos_dev);
-  else if (dtype == GM_BF16)
-    embed_tokens_kernel<bf16_raw><<<(int)g, 256, 0, st>>>(indices, (const bf16_raw*)token_weight, (const bf16_raw*)position_weight,
-                                                          (bf16_raw*)out, rows, seq_len, C, pos0, num_tokens, max_positions, pos_dev);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        embed_tokens_kernel<T><<<(int)g, 256, 0, st>>>(indices, (const T*)token_weight, (const T*)position_weight, (T*)out, rows, seq_len, C, pos0, num_tokens,
+                                                       max_positions, pos_dev);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -71,12 +68,10 @@ extern "C" int gm_embed_positions_grad(const void* g, float* out, int batch, int
   hipStream_t st = (hipStream_t)stream;
   long long gr = ((long long)max_positions * C + 255) / 256;
   if (gr > 4096) gr = 4096;
-  if (dtype == GM_F32)
-    embed_positions_grad_kernel<float><<<(int)gr, 256, 0, st>>>((const float*)g, out, batch, seq_len, C, max_positions);
-  else if (dtype == GM_BF16)
-    embed_positions_grad_kernel<bf16_raw><<<(int)gr, 256, 0, st>>>((const bf16_raw*)g, out, batch, seq_len, C, max_positions);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        embed_positions_grad_kernel<T><<<(int)gr, 256, 0, st>>>((const T*)g, out, batch, seq_len, C, max_positions);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -142,12 +137,10 @@ extern "C" int gm_sample_probs(const void* logits, long long ld, float* probs, l
   if (rows == 0) return 0;
   GM_REQUIRE(rows < (1LL << 31), "too many rows");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    sample_probs_kernel<float><<<(unsigned)rows, 64, 0, st>>>((const float*)logits, ld, probs, V, temperature, top_k, bos_index);
-  else if (dtype == GM_BF16)
-    sample_probs_kernel<bf16_raw><<<(unsigned)rows, 64, 0, st>>>((const bf16_raw*)logits, ld, probs, V, temperature, top_k, bos_index);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        sample_probs_kernel<T><<<(unsigned)rows, 64, 0, st>>>((const T*)logits, ld, probs, V, temperature, top_k, bos_index);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -233,12 +226,10 @@ extern "C" int gm_token_log_prob(const void* logits, long long ld, const long lo
   if (rows == 0) return 0;
   GM_REQUIRE(rows < (1LL << 31), "too many rows");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == GM_F32)
-    token_log_prob_kernel<float><<<(unsigned)rows, 64, 0, st>>>((const float*)logits, ld, target, out, V);
-  else if (dtype == GM_BF16)
-    token_log_prob_kernel<bf16_raw><<<(unsigned)rows, 64, 0, st>>>((const bf16_raw*)logits, ld, target, out, V);
-  else
-    GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        token_log_prob_kernel<T><<<(unsigned)rows, 64, 0, st>>>((const T*)logits, ld, target, out, V);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 

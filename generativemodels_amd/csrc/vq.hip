@@ -52,9 +52,10 @@ extern "C" int gm_vq_argmin(const void* x, long long x_ld, const float* embeddin
   if (tokens == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int grid = gm_cdiv(tokens, 256);
-  if (dtype == GM_F32) vq_argmin_kernel<float><<<grid, 256, 0, st>>>((const float*)x, x_ld, embedding, indices, tokens, num_embeddings, dim);
-  else if (dtype == GM_BF16) vq_argmin_kernel<bf16_raw><<<grid, 256, 0, st>>>((const bf16_raw*)x, x_ld, embedding, indices, tokens, num_embeddings, dim);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        vq_argmin_kernel<T><<<grid, 256, 0, st>>>((const T*)x, x_ld, embedding, indices, tokens, num_embeddings, dim);
+      })) GM_FAIL(-2, "unsupported dtype");
   GM_LAUNCH_CHECK();
 }
 
@@ -108,11 +109,10 @@ extern "C" int gm_vq_gather(const long long* indices, const float* embedding, vo
   if (g > VQ_GATHER_MAX_BLOCKS) g = VQ_GATHER_MAX_BLOCKS;
   double* part = sq_err_mean ? (double*)workspace : nullptr;
   const void* xx = sq_err_mean ? x : nullptr;
-  if (dtype == GM_F32)
-    vq_gather_kernel<float><<<(int)g, 256, 0, st>>>(indices, embedding, (float*)out, out_ld, (const float*)xx, x_ld, part, tokens, num_embeddings, dim);
-  else if (dtype == GM_BF16)
-    vq_gather_kernel<bf16_raw><<<(int)g, 256, 0, st>>>(indices, embedding, (bf16_raw*)out, out_ld, (const bf16_raw*)xx, x_ld, part, tokens, num_embeddings, dim);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        vq_gather_kernel<T><<<(int)g, 256, 0, st>>>(indices, embedding, (T*)out, out_ld, (const T*)xx, x_ld, part, tokens, num_embeddings, dim);
+      })) GM_FAIL(-2, "unsupported dtype");
   if (sq_err_mean) vq_sum_partials_kernel<<<1, 64, 0, st>>>(part, (int)g, 1.0 / ((double)tokens * dim), sq_err_mean);
   GM_LAUNCH_CHECK();
 }
@@ -214,11 +214,10 @@ extern "C" int gm_vq_ema_stats(const void* x, long long x_ld, const long long* i
   vq_ema_plan(tokens, num_embeddings, dim, &range, &nblk, &KC, &nchunk, &DT);
   const size_t smem = (size_t)KC * (dim + 1) * sizeof(float);
   dim3 grid((unsigned)nblk, (unsigned)nchunk);
-  if (dtype == GM_F32)
-    vq_ema_partial_kernel<float><<<grid, VQ_EMA_THREADS, smem, st>>>((const float*)x, x_ld, indices, tokens, range, num_embeddings, dim, KC, DT, workspace);
-  else if (dtype == GM_BF16)
-    vq_ema_partial_kernel<bf16_raw><<<grid, VQ_EMA_THREADS, smem, st>>>((const bf16_raw*)x, x_ld, indices, tokens, range, num_embeddings, dim, KC, DT, workspace);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!gm_dispatch_dtype(dtype, [&](auto tv) {
+        using T = typename decltype(tv)::type;
+        vq_ema_partial_kernel<T><<<grid, VQ_EMA_THREADS, smem, st>>>((const T*)x, x_ld, indices, tokens, range, num_embeddings, dim, KC, DT, workspace);
+      })) GM_FAIL(-2, "unsupported dtype");
   const long long n = (long long)num_embeddings * (dim + 1);
   long long g = (n + VQ_EMA_THREADS - 1) / VQ_EMA_THREADS;
   if (g > 1024) g = 1024;
