@@ -58,14 +58,15 @@ class GmConvDesc(C.Structure):
 
 class GmDecodeBlock(C.Structure):
     _fields_ = [("ln1_g", c_vp), ("ln1_b", c_vp), ("w_qkv", c_vp), ("b_qkv", c_vp), ("w_o", c_vp), ("b_o", c_vp), ("ln3_g", c_vp),
-                ("ln3_b", c_vp), ("w_1", c_vp), ("b_1", c_vp), ("w_2", c_vp), ("b_2", c_vp), ("k_cache", c_vp), ("v_cache", c_vp)]
+                ("ln3_b", c_vp), ("w_1", c_vp), ("b_1", c_vp), ("w_2", c_vp), ("b_2", c_vp), ("k_cache", c_vp), ("v_cache", c_vp),
+                ("ln2_g", c_vp), ("ln2_b", c_vp), ("w_cq", c_vp), ("b_cq", c_vp), ("w_co", c_vp), ("b_co", c_vp), ("ck", c_vp), ("cv", c_vp)]
 
 
 class GmDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("C", C.c_int), ("M", C.c_int), ("heads", C.c_int), ("depth", C.c_int), ("max_len", C.c_int),
                 ("num_tokens", C.c_int), ("dtype", C.c_int), ("ln_eps", C.c_float), ("pos", C.c_int), ("tokens", c_vp),
                 ("tok_emb", c_vp), ("pos_emb", c_vp), ("blocks", C.POINTER(GmDecodeBlock)), ("w_logits", c_vp), ("b_logits", c_vp),
-                ("logits", c_vp), ("scratch", c_vp), ("scratch_bytes", c_ll), ("pos_dev", c_vp)]
+                ("logits", c_vp), ("scratch", c_vp), ("scratch_bytes", c_ll), ("pos_dev", c_vp), ("ctx_len", C.c_int)]
 
 
 class GmAttnDesc(C.Structure):
@@ -158,6 +159,7 @@ PROTOTYPES = {
     "gm_decode_advance": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, c_ll, c_vp]),
     "gm_transformer_decode_step": (C.c_int, [C.POINTER(GmDecodeDesc), c_vp]),
     "gm_transformer_decode_plan": (C.c_int, [C.POINTER(GmDecodeDesc), C.POINTER(C.c_int)]),
+    "gm_decode_cross_route": (C.c_int, [C.POINTER(GmDecodeDesc)]),
     "gm_embed_tokens": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_embed_positions_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_sample_probs": (C.c_int, [c_vp, c_ll, c_vp, c_ll, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_vp]),

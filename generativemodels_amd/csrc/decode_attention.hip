@@ -5,6 +5,7 @@
 //   attn_decode_split_kernel     long windows: the keys cut into GM_DECODE_KV_SPLITS ranges, one work-group each (attn_range_body), partials to a workspace
 //   attn_decode_combine_kernel   ... merged in range order (kv_merge_one; the out-projection's prologue in rows_gemm.hip can merge them instead)
 //   qkv_attn_rows_kernel         LayerNorm + q | k | v projection + one key range in ONE launch, with its select / plan / launch functions
+//   cross_attn_rows_kernel       cross attention: LayerNorm + one head's q projection + all keys of the projected context in ONE launch, likewise
 #include <cstdlib>
 #include "conv_common.h"
 #include "decode_common.h"
@@ -456,6 +457,145 @@ extern "C" int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream) 
     if (ng == 12 && um == 2) GM_QKV_LAUNCH(float, 12, 2);
   }
 #undef GM_QKV_LAUNCH
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Cross attention of the decode step: LayerNorm2 + head h's q projection + the 1 x Lc attention over the projected context in ONE launch, built like
+// qkv_attn_rows_kernel above: work-group b * H + h normalises the residual-stream row of sample b, multiplies it with head h's dh rows of to_q (K chunks
+// dealt to the four waves, every weight fragment requested at entry, the partial sums met in LDS in wave order), keeps q in LDS (scaled, rounded through T
+// like the stored q of the composed form) and runs attn_range_body over ALL Lc keys of ck / cv (read only).  The context is short (tens of keys: one
+// range) and does not grow, so there is no key split and no merge: the work-group normalises its own output and stores it for the out-projection GEMM.
+// NG = dh / 16 output groups, UM = K chunks per wave (host: C % BK == 0, ceil(C / BK / 4) <= UM).  Fixed summation order, no atomics.
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <typename T, int NG, int UM>
+__global__ __launch_bounds__(256) void cross_attn_rows_kernel(CrossAttnArgs a) {
+  constexpr int BK = ConvTraits<T>::BK, VECW = ConvTraits<T>::VECW;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int C = a.C, dh = a.dh;
+  float* sc = reinterpret_cast<float*>(smem);    // [sc_elems] scores, then probabilities; later the [KL][dh] partial table
+  float* qs = sc + a.sc_elems;                   // [dh]
+  float* red = qs + dh;                          // [8]
+  float* outp = red + 8;                         // [dh] un-normalised output
+  float* ml = outp + dh;                         // [4] softmax maximum, denominator
+  float* xrow = ml + 4;                          // [C]
+  float* part = xrow + C;                        // [4][dh]
+  T* xn = reinterpret_cast<T*>(part + 4 * dh);   // [C] LayerNorm'ed row (16-byte aligned: every count above is a multiple of 4 floats)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, q4 = lane >> 4;
+  const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
+  const int nchunks = C / BK, cout_pad = (C + 15) & ~15;
+  // ---- requested at entry: every weight fragment of this wave, this thread's bias ------------------------------------------------------------
+  const T* W = reinterpret_cast<const T*>(a.w);
+  uint4 wfr[NG][UM];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int co = h * dh + g * 16 + l15;
+#pragma unroll
+    for (int u = 0; u < UM; ++u) {
+      const int c = wave + 4 * u < nchunks ? wave + 4 * u : nchunks - 1;
+      wfr[g][u] = *reinterpret_cast<const uint4*>(W + ((long long)c * cout_pad + co) * BK + q4 * VECW);
+    }
+  }
+  const int tt = tid < dh ? tid : 0;
+  const float bval = (a.bias ? a.bias : reinterpret_cast<const float*>(a.w))[a.bias ? h * dh + tt : 0];
+  // ---- the residual-stream row of sample b, LayerNorm (two-pass statistics, like the reference's fp32 computation) -----------------------------
+  for (int idx = tid; idx < C; idx += 256) xrow[idx] = ElemIO<T>::ld(reinterpret_cast<const T*>(a.x) + (long long)b * C + idx);
+  __syncthreads();
+  float part_s = 0.f;
+  for (int idx = tid; idx < C; idx += 256) part_s += xrow[idx];
+  part_s = wave_sum(part_s);
+  if (lane == 0) red[wave] = part_s;
+  __syncthreads();
+  const float mean = (((red[0] + red[1]) + red[2]) + red[3]) / (float)C;
+  float part_q = 0.f;
+  for (int idx = tid; idx < C; idx += 256) part_q += (xrow[idx] - mean) * (xrow[idx] - mean);
+  part_q = wave_sum(part_q);
+  if (lane == 0) red[4 + wave] = part_q;
+  __syncthreads();
+  const float rstd = 1.0f / sqrtf((((red[4] + red[5]) + red[6]) + red[7]) / (float)C + a.ln_eps);
+  for (int idx = tid; idx < C; idx += 256)
+    ElemIO<T>::st(xn + idx, (xrow[idx] - mean) * rstd * a.ln_g[idx] + (a.ln_b ? a.ln_b[idx] : 0.f));
+  __syncthreads();
+  // ---- q of head h: this wave's K chunks, then the four waves' partial sums in wave order --------------------------------------------------------
+  f32x4_t acc[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) acc[g] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < UM; ++u) {
+    const int c = wave + 4 * u;
+    if (c < nchunks) {  // (wave-uniform)
+      const uint4 xv = *reinterpret_cast<const uint4*>(xn + c * BK + q4 * VECW);
+      const uint4 xf = make_uint4(l15 == 0 ? xv.x : 0u, l15 == 0 ? xv.y : 0u, l15 == 0 ? xv.z : 0u, l15 == 0 ? xv.w : 0u);  // MFMA column 0 = the row
+#pragma unroll
+      for (int g = 0; g < NG; ++g) Mma<T>::run(wfr[g][u], xf, acc[g]);
+    }
+  }
+  if (l15 == 0) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) part[wave * dh + g * 16 + 4 * q4 + i] = acc[g][i];
+  }
+  __syncthreads();
+  if (tid < dh) {
+    const float val = (((part[tid] + part[dh + tid]) + part[2 * dh + tid]) + part[3 * dh + tid]) + (a.bias ? bval : 0.f);
+    T r;
+    ElemIO<T>::st(&r, val);
+    qs[tid] = ElemIO<T>::ld(&r) * a.scale;
+  }
+  __syncthreads();
+  // ---- softmax(q Kc^T) Vc over the Lc context keys of sample b, head h ----------------------------------------------------------------------------
+  const T* K = reinterpret_cast<const T*>(a.ck) + (long long)b * a.Lc * C + h * dh;
+  const T* V = reinterpret_cast<const T*>(a.cv) + (long long)b * a.Lc * C + h * dh;
+  attn_range_body<T>(K, C, V, C, a.Lc, dh, qs, sc, red, outp, ml, ml + 1, tid);
+  __syncthreads();
+  if (tid < dh) ElemIO<T>::st(reinterpret_cast<T*>(a.o) + (long long)b * C + h * dh + tid, outp[tid] * (1.0f / ml[1]));
+}
+
+// Which instantiation takes this geometry: 1 and (*ng, *um) = its template arguments (and *sc_elems, *smem when given), 0 = none.  The one decision
+// both the launch below and the decode step's cross route (decode_step.hip: gm_decode_cross_route) consult.
+static int cross_attn_rows_select(const CrossAttnArgs& a, int dtype, int* ng_out, int* um_out, int* sc_out, size_t* smem_out) {
+  static const bool on = !(getenv("GM_DECODE_CROSS_FUSE") && getenv("GM_DECODE_CROSS_FUSE")[0] == '0');  // bench switch (tools/bench_c5.py)
+  if (!on || (dtype != GM_F32 && dtype != GM_BF16)) return 0;
+  const int bk = dtype == GM_F32 ? 16 : 32, vecw = dtype == GM_F32 ? 4 : 8;
+  if (a.H <= 0 || a.dh <= 0 || a.C != a.H * a.dh || a.C % bk) return 0;
+  if (a.dh != 16 && a.dh != 32 && a.dh != 64 && a.dh != 128) return 0;  // NG in {1, 2, 4, 8}
+  if (a.Lc < 1 || a.Lc > GM_DECODE_CROSS_MAX_FUSED_CTX || a.B < 1 || (long long)a.B * a.H > 65535) return 0;
+  const int ng = a.dh / 16, nchunks = a.C / bk, need = (nchunks + 3) / 4;
+  const int um = need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 0;
+  if (!um || ng * um > 32) return 0;  // (the weight fragments are 4 registers each)
+  const int keys = (a.Lc + 3) & ~3;
+  const int sc_elems = keys > 256 * vecw ? keys : 256 * vecw;  // the score buffer doubles as the [KL][dh] partial table
+  if (ng_out) *ng_out = ng;
+  if (um_out) *um_out = um;
+  if (sc_out) *sc_out = sc_elems;
+  if (smem_out) *smem_out = (size_t)(sc_elems + a.dh + 8 + a.dh + 4 + a.C + 4 * a.dh) * sizeof(float) + (size_t)a.C * (dtype == GM_F32 ? 4 : 2);
+  return 1;
+}
+extern "C" int gm_cross_attn_rows_plan(const CrossAttnArgs* ap, int dtype, int* ng, int* um) {
+  return cross_attn_rows_select(*ap, dtype, ng, um, nullptr, nullptr);
+}
+
+extern "C" int gm_cross_attn_rows(const CrossAttnArgs* ap, int dtype, void* stream) {
+  const CrossAttnArgs& a = *ap;
+  int ng = 0, um = 0, sc_elems = 0;
+  size_t smem = 0;
+  if (!a.x || !a.ln_g || !a.w || !a.ck || !a.cv || !a.o) return 0;
+  if (!cross_attn_rows_select(a, dtype, &ng, &um, &sc_elems, &smem)) return 0;
+  CrossAttnArgs k = a;
+  k.sc_elems = sc_elems;
+  hipStream_t st = (hipStream_t)stream;
+#define GM_CROSS_LAUNCH(NG, UM)                                                                          \
+  if (ng == NG && um == UM) {                                                                            \
+    if (dtype == GM_BF16) cross_attn_rows_kernel<bf16_raw, NG, UM><<<a.B * a.H, 256, smem, st>>>(k);     \
+    else cross_attn_rows_kernel<float, NG, UM><<<a.B * a.H, 256, smem, st>>>(k);                         \
+    return hipGetLastError() == hipSuccess ? 1 : -1;                                                     \
+  }
+  GM_CROSS_LAUNCH(1, 2) GM_CROSS_LAUNCH(1, 4) GM_CROSS_LAUNCH(1, 8)
+  GM_CROSS_LAUNCH(2, 2) GM_CROSS_LAUNCH(2, 4) GM_CROSS_LAUNCH(2, 8)
+  GM_CROSS_LAUNCH(4, 2) GM_CROSS_LAUNCH(4, 4) GM_CROSS_LAUNCH(4, 8)
+  GM_CROSS_LAUNCH(8, 2) GM_CROSS_LAUNCH(8, 4)
+#undef GM_CROSS_LAUNCH
   return 0;
 }
 

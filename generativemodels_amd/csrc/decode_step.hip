@@ -8,7 +8,13 @@
 // the previous block's MLP partials] -> [out_proj + residual, its prologue merging the attention ranges] -> [LayerNorm + MLP up + GELU + MLP down
 // as K-slice partials] -- and the round-2 sequence (or a partly fused one) otherwise
 // (reference semantics: networks/nets/transformer.py:98-106, blocks/transformerblock.py:86-91, blocks/selfattention.py:98-147).
+// Cross attention (GmDecodeDesc.ctx_len > 0; until then such models were decoded op by op from Python, re-projecting the whole context through to_k / to_v
+// for every token): between the out-projection and the MLP every block adds out_proj(softmax(scale q Kc^T) Vc), q = to_q(LayerNorm2(x)), over context keys /
+// values the caller projected ONCE per cache.  Two added launches per block where the fused kernel of decode_attention.hip takes the geometry
+// ([LayerNorm2 + q + 1 x Lc attention] -> [out_proj + residual]), three otherwise ([LayerNorm2 + q GEMM] -> [gm_attention_forward, one query] ->
+// [out_proj + residual]): gm_decode_cross_route.  The stage reads the stream from x1 and leaves it in x0, after which the two buffers swap roles.
 #include <cstdlib>
+#include <utility>
 #include "attn_common.h"
 #include "conv_common.h"
 
@@ -88,6 +94,35 @@ static void decode_plan(const GmDecodeDesc& d, int blk, const QkvAttnArgs& qa, b
   f[GM_DECODE_PLAN_KSPLIT_LOGITS] = ks_c;
 }
 
+// ---- the cross-attention stage -------------------------------------------------------------------------------------------------------------
+// the fused kernel's arguments for block `blk`: the stream row `x` in, the attention output `o` (before the out-projection) out
+static CrossAttnArgs decode_cross_args(const GmDecodeDesc& d, int blk, const void* x, void* o) {
+  const GmDecodeBlock& b = d.blocks[blk];
+  CrossAttnArgs ca = {};
+  ca.x = x; ca.ln_g = b.ln2_g; ca.ln_b = b.ln2_b; ca.ln_eps = d.ln_eps;
+  ca.w = b.w_cq; ca.bias = b.b_cq; ca.ck = b.ck; ca.cv = b.cv; ca.o = o;
+  ca.B = d.B; ca.H = d.heads; ca.C = d.C; ca.dh = d.C / d.heads; ca.Lc = d.ctx_len;
+  ca.scale = 1.0f / sqrtf((float)(d.C / d.heads));
+  return ca;
+}
+
+// Host only: GM_DECODE_CROSS_* for `dp`, from the geometry and the dtype alone (the same for every block), or a negative error.
+extern "C" int gm_decode_cross_route(const GmDecodeDesc* dp) {
+  GM_REQUIRE(dp, "null descriptor");
+  const GmDecodeDesc& d = *dp;
+  GM_REQUIRE(d.ctx_len >= 0, "negative context length");
+  if (d.ctx_len == 0) return GM_DECODE_CROSS_NONE;
+  GM_REQUIRE(d.B > 0 && d.C > 0 && d.heads > 0 && d.C % d.heads == 0 && d.depth > 0 && d.blocks, "bad geometry");
+  for (int i = 0; i < d.depth; ++i) {
+    const GmDecodeBlock& b = d.blocks[i];
+    GM_REQUIRE(b.ln2_g && b.w_cq && b.w_co && b.ck && b.cv, "null cross-attention pointer in a block (ctx_len > 0)");
+  }
+  const CrossAttnArgs ca = decode_cross_args(d, 0, nullptr, nullptr);
+  int ng = 0, um = 0;
+  // (more than 16 rows: the out-projection behind the kernel leaves the K-split GEMM, and B * heads work-groups stop being a handful)
+  return d.B <= 16 && gm_cross_attn_rows_plan(&ca, d.dtype, &ng, &um) == 1 ? GM_DECODE_CROSS_FUSED : GM_DECODE_CROSS_COMPOSED;
+}
+
 // the descriptor checks shared by the step and its plan (a macro: a failure names the entry point that was called)
 #define GM_DECODE_CHECK(dp)                                                                                                               \
   do {                                                                                                                                    \
@@ -131,6 +166,8 @@ extern "C" int gm_transformer_decode_plan(const GmDecodeDesc* dp, int* flags) {
 
 extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) {
   GM_DECODE_CHECK(dp);
+  const int cross = gm_decode_cross_route(dp);  // (validates the cross fields of ALL blocks before the first launch)
+  if (cross < 0) return cross;
   const GmDecodeDesc& d = *dp;
   const int hpos = d.pos_dev ? 0 : d.pos;  // host-side position (0 when the device supplies it)
   const long long es = elt(d.dtype);
@@ -199,6 +236,30 @@ extern "C" int gm_transformer_decode_step(const GmDecodeDesc* dp, void* stream) 
       return rc;
     }
     if (!out_done && (rc = linear_rows(y, C, b.w_o, b.b_o, x0, C, x1, C, d.B, C, C, 0, d.dtype, nullptr, stream))) return rc;
+    if (cross != GM_DECODE_CROSS_NONE) {
+      // the stream is in x1; x0 is dead since the out-projection above read it as its residual: the stage leaves x1 + out_proj(attention) there and
+      // the two buffers swap roles, so the MLP below, the next block's prologue and to_logits find the stream where they expect it (x1)
+      if (cross == GM_DECODE_CROSS_FUSED) {
+        const CrossAttnArgs ca = decode_cross_args(d, i, x1, y);
+        rc = gm_cross_attn_rows(&ca, d.dtype, stream);
+        if (rc < 0) GM_FAIL(rc, "launch of the fused cross-attention kernel");
+        GM_REQUIRE(rc == 1, "the fused cross-attention launch disagrees with the route");
+      } else {
+        GmRowsFused ln2 = {};
+        ln2.ln_g = b.ln2_g; ln2.ln_b = b.ln2_b; ln2.ln_eps = d.ln_eps;
+        if ((rc = linear_rows(x1, C, b.w_cq, b.b_cq, nullptr, 0, w.h, C, d.B, C, C, 0, d.dtype, &ln2, stream))) return rc;
+        GmAttnDesc ct = {};
+        ct.q = w.h; ct.q_ld = C;
+        ct.k = b.ck; ct.k_ld = C; ct.k_bs = (long long)d.ctx_len * C;
+        ct.v = b.cv; ct.v_ld = C; ct.v_bs = (long long)d.ctx_len * C;
+        ct.o = y; ct.o_ld = C;
+        ct.B = d.B; ct.H = d.heads; ct.Lq = 1; ct.Lk = d.ctx_len; ct.dh = C / d.heads;
+        ct.scale = scale; ct.dtype = d.dtype;
+        if ((rc = gm_attention_forward(&ct, stream))) return rc;
+      }
+      if ((rc = linear_rows(y, C, b.w_co, b.b_co, x1, C, x0, C, d.B, C, C, 0, d.dtype, nullptr, stream))) return rc;
+      std::swap(x0, x1);
+    }
     if (mlp_fuse) {
       if ((rc = gm_mlp_rows(x1, b.ln3_g, b.ln3_b, d.ln_eps, b.w_1, b.b_1, b.w_2, mlp_p, d.B, C, d.M, 6, d.dtype, stream))) return rc;
       continue;

@@ -86,5 +86,17 @@ struct QkvAttnArgs {
 };
 int gm_qkv_attn_rows(const QkvAttnArgs* ap, int dtype, void* stream);
 int gm_qkv_attn_rows_plan(const QkvAttnArgs* ap, int dtype, int* ng, int* um);  // which instantiation would take it; launches nothing
+// LayerNorm + one head's q projection + the 1 x Lc attention over projected context keys / values in one launch (cross_attn_rows_kernel, by value)
+struct CrossAttnArgs {
+  const void* x;                                                        // [B][C] residual-stream rows
+  const float* ln_g; const float* ln_b; float ln_eps;
+  const void* w; const float* bias;                                     // packed [chunk][C pad 16][BK]; fp32 [C] or null
+  const void* ck; const void* cv;                                       // [B][Lc][C]
+  void* o;                                                              // [B][C] attention output (before the out-projection)
+  int B, H, C, dh, Lc;
+  float scale; int sc_elems;
+};
+int gm_cross_attn_rows(const CrossAttnArgs* ap, int dtype, void* stream);        // 1 = launched, 0 = not this kernel's case, < 0 = error
+int gm_cross_attn_rows_plan(const CrossAttnArgs* ap, int dtype, int* ng, int* um);  // 1 and the instantiation that would take it, or 0; launches nothing
 
 }  // extern "C"

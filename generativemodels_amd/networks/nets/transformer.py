@@ -4,7 +4,8 @@ reference's generative/networks/nets/transformer.py:20-106.
 Beyond the reference's full-sequence `forward`, the module offers an incremental decoding API over a KV cache
 (`new_cache` / `step`): the reference's sampling loop re-runs the whole prefix for every new token (O(L^3) attention work,
 ≈ 390-580 TFLOP for 4096 tokens); with the cache a token costs one row through every GEMM and one
-1 x t attention per block."""
+1 x t attention per block.  With cross attention the cache also holds every block's projected context keys / values (`ck`, `cv`),
+computed once per context: a token then adds one query row and one 1 x Lc attention per block, inside the same native step."""
 from __future__ import annotations
 
 from typing import Optional
@@ -104,10 +105,44 @@ class DecoderOnlyTransformer(nn.Module):
         return A.linear(h, self.to_logits.weight, self.to_logits.bias)
 
     # ---- incremental decoding ------------------------------------------------------------------------------------------------------
-    def new_cache(self, batch: int, device) -> list:
+    def new_cache(self, batch: int, device, context: torch.Tensor | None = None) -> list:
+        """Per block the (B, max_seq_len, C) key / value buffers of the self attention; with a `context` (cross-attention models) also `ck` / `cv`,
+        its projections through the block's cross_attn.to_k / to_v (see `_project_context`)."""
         dt = self.to_logits.weight.dtype
         shape = (batch, self.max_seq_len, self.attn_layers_dim)
-        return [dict(k=torch.empty(shape, dtype=dt, device=device), v=torch.empty(shape, dtype=dt, device=device)) for _ in self.blocks]
+        cache = [dict(k=torch.empty(shape, dtype=dt, device=device), v=torch.empty(shape, dtype=dt, device=device)) for _ in self.blocks]
+        if context is not None:
+            self._project_context(cache, context)
+        return cache
+
+    def _project_context(self, cache: list, context: torch.Tensor) -> None:
+        """ck / cv = cross_attn.to_k / to_v of the cast context, dense (B, Lc, C) in the model dtype, once per context instead of once per token
+        (the context does not change during a sample).  Every entry remembers the tensor and the version it was projected from; a projection
+        of the same shape is written into the buffers the cache already holds, so a native table or a captured graph keeps pointing at it."""
+        if not self.with_cross_attention:
+            raise ValueError("context given but the model was built without cross attention")
+        ops.require_device(context)
+        b, c = cache[0]["k"].shape[0], self.attn_layers_dim
+        if context.dim() != 3 or context.shape[0] != b or context.shape[2] != c or context.shape[1] < 1:
+            raise ValueError(f"expected a ({b}, Lc, {c}) context, got {tuple(context.shape)}")
+        with torch.no_grad():
+            ctx = self._context(context)
+            for blk, ent in zip(self.blocks, cache):
+                a = blk.cross_attn
+                for name, lin in (("ck", a.to_k), ("cv", a.to_v)):
+                    t = ops.linear(ctx, lin.weight, lin.bias).contiguous()
+                    if name in ent and ent[name].shape == t.shape:
+                        ent[name].copy_(t)
+                    else:
+                        ent[name] = t
+                        cache[0].pop("_native", None)  # (the table points at the old buffers)
+                ent["ctx_src"], ent["ctx_version"] = context, context._version
+
+    def _ensure_context(self, cache: list, context: torch.Tensor) -> None:
+        """Projects lazily, and again for another context tensor or the same one changed in place: the step never serves stale keys."""
+        ent = cache[0]
+        if "ck" not in ent or ent.get("ctx_src") is not context or ent.get("ctx_version") != context._version:
+            self._project_context(cache, context)
 
     def _native_table(self, cache: list):
         """Block-parameter table of gm_transformer_decode_step for this cache (built once per cache; keeps every tensor it points to)."""
@@ -142,6 +177,12 @@ class DecoderOnlyTransformer(nn.Module):
             cb.w_1, cb.b_1 = packed(blk.mlp.linear1.weight), f32(blk.mlp.linear1.bias)
             cb.w_2, cb.b_2 = packed(blk.mlp.linear2.weight), f32(blk.mlp.linear2.bias)
             cb.k_cache, cb.v_cache = ent["k"].data_ptr(), ent["v"].data_ptr()
+            if "ck" in ent:  # cross attention over the projected context (GmDecodeDesc.ctx_len > 0)
+                x = blk.cross_attn
+                cb.ln2_g, cb.ln2_b = f32(blk.norm2.weight), f32(blk.norm2.bias)
+                cb.w_cq, cb.b_cq = packed(x.to_q.weight), f32(x.to_q.bias)
+                cb.w_co, cb.b_co = packed(x.out_proj.weight), f32(x.out_proj.bias)
+                cb.ck, cb.cv = ent["ck"].data_ptr(), ent["cv"].data_ptr()
         b = cache[0]["k"].shape[0]
         m = self.blocks[0].mlp.linear1.weight.shape[0]
         d = GmDecodeDesc()
@@ -150,6 +191,7 @@ class DecoderOnlyTransformer(nn.Module):
         tok, pos = self.token_embeddings.weight.detach().contiguous(), self.position_embeddings.embedding.weight.detach().contiguous()
         d.tok_emb, d.pos_emb = tok.data_ptr(), pos.data_ptr()
         d.blocks = blocks
+        d.ctx_len = cache[0]["ck"].shape[1] if "ck" in cache[0] else 0
         d.w_logits, d.b_logits = packed(self.to_logits.weight), f32(self.to_logits.bias)
         nbytes = lib().gm_decode_scratch_bytes(b, c, m, d.dtype)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -162,9 +204,10 @@ class DecoderOnlyTransformer(nn.Module):
     def step_from_device_state(self, tokens: torch.Tensor, pos_dev: torch.Tensor, cache: list, logits: torch.Tensor) -> None:
         """The native decode step with the position read from `pos_dev` (int32, 1 element, on the device) at run time and the logits
         written into the caller's (B, num_tokens) buffer: every argument is a fixed device address, so the call can be captured into
-        a HIP graph and replayed once per token (VQVAETransformerInferer.sample).  No cross attention."""
-        if self.with_cross_attention:
-            raise ValueError("the graph-replayable step covers models without cross attention")
+        a HIP graph and replayed once per token (VQVAETransformerInferer.sample).  A cross-attention model attends to the context
+        projections the cache holds (`new_cache(batch, device, context)` or an earlier `step` with the context)."""
+        if self.with_cross_attention and "ck" not in cache[0]:
+            raise ValueError("the graph-replayable step of a cross-attention model needs a cache that holds the context projections")
         ops.require_device(tokens, pos_dev, logits)
         if tokens.dtype != torch.long or pos_dev.dtype != torch.int32 or logits.dtype != self.to_logits.weight.dtype or not logits.is_contiguous():
             raise TypeError("tokens int64, pos_dev int32, logits in the model dtype (contiguous)")
@@ -182,9 +225,11 @@ class DecoderOnlyTransformer(nn.Module):
         if tokens.shape[1] != 1 or not 0 <= pos < self.max_seq_len:
             raise ValueError("step takes one token per sequence at a position inside the context window")
         with torch.no_grad():
-            if not self.with_cross_attention and self.native_step:
-                # the whole token step (38-62 launches) is enqueued by one native call: 20 us of interpreter work per launch made
-                # the per-op path below as slow as recomputing the prefix (tools/bench_c5.py)
+            if self.native_step and (context is not None or not self.with_cross_attention):
+                # the whole token step (38-62 launches, 2-3 more per block with cross attention) is enqueued by one native call: 20 us of
+                # interpreter work per launch made the per-op path below as slow as recomputing the prefix (tools/bench_c5.py)
+                if context is not None:
+                    self._ensure_context(cache, context)
                 d = self._native_table(cache)["desc"]
                 tokens = tokens.contiguous()
                 logits = torch.empty((tokens.shape[0], self.num_tokens), dtype=self.to_logits.weight.dtype, device=tokens.device)

@@ -372,9 +372,13 @@ int gm_rows_gemm(const GmRowsDesc* d, void* stream);
 int gm_rows_gemm_route(const GmRowsDesc* d);
 
 /* One KV-cache decoding step of the decoder-only transformer issued natively (38-62 launches back to back, by how many of the fused kernels of rows_gemm.hip / decode_attention.hip take the geometry): embed the fed token at
- * `pos`, per block LayerNorm -> q|k|v -> append k, v to the caches -> 1 x (pos+1) attention -> out_proj + x -> LayerNorm -> MLP(GELU) + x,
- * then to_logits (networks/nets/transformer.py:98-106, blocks/transformerblock.py:86-91, blocks/selfattention.py:98-147; no cross
- * attention).  Weights are gm_pack_conv_weight images of the nn.Linear matrices (q, k, v stacked along the output dim). */
+ * `pos`, per block LayerNorm -> q|k|v -> append k, v to the caches -> 1 x (pos+1) attention -> out_proj + x -> [cross attention] -> LayerNorm -> MLP(GELU) + x,
+ * then to_logits (networks/nets/transformer.py:98-106, blocks/transformerblock.py:86-91, blocks/selfattention.py:98-147).
+ * Weights are gm_pack_conv_weight images of the nn.Linear matrices (q, k, v stacked along the output dim).
+ * Cross attention (ctx_len > 0): between the self-attention's out-projection and the MLP every block adds out_proj(softmax(scale q Kc^T) Vc) with
+ * q = to_q(LayerNorm2(x)) over ctx_len context keys / values the CALLER projected once (ck = to_k(context), cv = to_v(context): dense [B][ctx_len][C], never
+ * written by the step).  It does not depend on the position: a host-position and a device-position step run the same cross kernels.  ctx_len == 0: no
+ * cross attention, the blocks' cross fields are never read. */
 typedef struct GmDecodeBlock {
   const float *ln1_g, *ln1_b;
   const void* w_qkv; const float* b_qkv;
@@ -383,6 +387,10 @@ typedef struct GmDecodeBlock {
   const void* w_1; const float* b_1;
   const void* w_2; const float* b_2;
   void* k_cache; void* v_cache;      /* [B][max_len][C] */
+  const float *ln2_g, *ln2_b;        /* cross attention (read when GmDecodeDesc.ctx_len > 0): LayerNorm2 ... */
+  const void* w_cq; const float* b_cq;  /* ... to_q (packed [C][C]; bias fp32 [C] or NULL) ... */
+  const void* w_co; const float* b_co;  /* ... out_proj ... */
+  const void* ck; const void* cv;    /* ... and the projected context keys / values [B][ctx_len][C], dtype */
 } GmDecodeBlock;
 typedef struct GmDecodeDesc {
   int B, C, M, heads, depth, max_len, num_tokens, dtype;
@@ -395,6 +403,7 @@ typedef struct GmDecodeDesc {
   void* logits;                      /* [B][num_tokens], dtype */
   void* scratch; long long scratch_bytes;
   const int* pos_dev;                /* optional: position read from device memory at run time (for HIP-graph replay); `pos` is then ignored */
+  int ctx_len;                       /* context keys per sample of the cross attention; 0 = none */
 } GmDecodeDesc;
 long long gm_decode_scratch_bytes(int B, int C, int M, int dtype);
 int gm_transformer_decode_step(const GmDecodeDesc* d, void* stream);
@@ -423,6 +432,19 @@ int gm_transformer_decode_step(const GmDecodeDesc* d, void* stream);
 #define GM_DECODE_ENTRY_HOST_POS 1        /* single-launch attention through gm_attention_forward */
 #define GM_DECODE_ENTRY_DEVICE_POS 2      /* single-launch attention reading the key count on the device */
 int gm_transformer_decode_plan(const GmDecodeDesc* d, int* flags);
+/* The route of the step's cross-attention stage, host only (the step consults the same function, for all blocks, before its first launch); the twelve plan
+ * flags above do not depend on ctx_len.  A negative error (message: gm_last_error) for ctx_len < 0, or for ctx_len > 0 with a null ln2_g / w_cq / w_co /
+ * ck / cv in any block.  FUSED: LayerNorm2 + the head's q projection + the 1 x ctx_len attention as one launch per block (one work-group per (sample,
+ * head)), then the out-projection + residual on the row GEMM -- head dim 16, 32, 64 or 128, C a multiple of the MFMA K step (32 bf16 / 16 fp32) with
+ * at most 32 K steps (16 at head dim 128), ctx_len <= GM_DECODE_CROSS_MAX_FUSED_CTX, at most 16 rows.  COMPOSED: everything else -- LayerNorm2 + to_q on the row GEMM,
+ * gm_attention_forward with one query, the out-projection. */
+#define GM_DECODE_CROSS_NONE 0
+#define GM_DECODE_CROSS_FUSED 1
+#define GM_DECODE_CROSS_COMPOSED 2
+/* fp32 scores of the fused kernel live in LDS: 4096 keys are 16 KiB, which with the row, the query and the partial sums (< 13 KiB at C = 512) keeps a
+ * work-group under a quarter of the CU's 160 KiB and under the 64 KiB a launch may request without opting in */
+#define GM_DECODE_CROSS_MAX_FUSED_CTX 4096
+int gm_decode_cross_route(const GmDecodeDesc* d);
 /* after a draw: seq[b][*pos + 1] = idx[b]; tokens[b] = idx[b]; *pos += 1 (inferer.py:1237-1239 kept on the device) */
 int gm_decode_advance(int* pos, long long* tokens, const long long* idx, long long* seq, int B, long long seq_ld, void* stream);
 
