@@ -26,8 +26,8 @@ def __getattr__(name):
         return GraphedForwardBackward
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
-_MIRRORED = ["", ".networks", ".networks.nets", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",
-             ".inferers", ".utils", ".metrics", ".losses"]
+_MIRRORED = ["", ".networks", ".networks.nets", ".networks.nets.patchgan_discriminator", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",
+             ".inferers", ".utils", ".metrics", ".losses", ".losses.adversarial_loss"]
 
 
 def install_as_generative(force: bool = False) -> None:

@@ -214,6 +214,13 @@ PROTOTYPES = {
     "gm_dft_lines": (C.c_int, [C.POINTER(GmDftDesc), c_vp]),
     "gm_spectral_loss_partials": (C.c_int, [c_ll]),
     "gm_spectral_loss": (C.c_int, [c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_double, c_vp]),
+    "gm_bn_finalize": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int, c_ll, c_vp, c_vp, C.c_float, C.c_float, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gm_bn_apply": (C.c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_float, C.c_int, c_vp]),
+    "gm_bn_bwd_stats_slots": (c_ll, [c_ll]),
+    "gm_bn_bwd_stats": (C.c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_float, c_vp, C.c_int, c_vp]),
+    "gm_bn_bwd_finalize": (C.c_int, [c_vp, C.c_int, C.c_int, c_ll, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gm_bn_bwd_apply": (C.c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_float, C.c_int, c_vp]),
+    "gm_patch_adv_loss": (C.c_int, [c_vp, c_ll, C.c_int, C.c_int, C.c_float, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp]),
 }
 
 _lib = None

@@ -17,6 +17,10 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
                   causal flag, backward always on the causal fp32-MFMA flash kernels (route "causal", head dims zero-padded to 16 .. 256)
   embed_tokens    token + position embedding; both tables' gradients as fixed-order sums (gm_vq_ema_stats, gm_embed_positions_grad), no atomics
   resize          forward: F.interpolate (every mode) as one launch of the separable tap kernel; backward: the same kernel on the transposed tables
+  avg_pool        nn.AvgPool{2,3}d at stride 2 on the same tap kernel, from explicit tap tables (resize_plan.avg_pool_plan)
+  batch_norm_act  forward: per-channel statistics -> gm_bn_finalize (tables + running buffers) -> one apply pass (+ LeakyReLU / ReLU)
+                  backward: gm_bn_bwd_stats / _finalize / _apply from the call's own tables (dx, dgamma, dbeta)
+  patch_adv_loss  PatchAdversarialLoss over one discriminator output: activation, criterion, reduction and gradient in gm_patch_adv_loss
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -28,7 +32,7 @@ import torch
 
 from . import ops
 
-__all__ = ["cast", "scale", "leaky_relu", "kld", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -946,3 +950,96 @@ def spectral_loss(x: torch.Tensor, y: torch.Tensor, fft_signal_size=None, fft_no
         raise ValueError(f"spectral_loss: reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
     ops.require_device(x, y)
     return _SpectralLoss.apply(x, y, ops.spectral_plan(x, fft_signal_size, fft_norm), reduction)
+
+
+class _BatchNormAct(torch.autograd.Function):
+    """y = LeakyReLU_slope(BatchNorm(x)) (slope None: no activation; 0: ReLU) over the batch and every spatial position of an arena tensor.  The tables of
+    THIS call (scale, shift, mean, invstd) are what the backward reads: a second forward before the backward (D(fake), D(real), one backward) overwrites
+    the running buffers in place, never these.  Parameters, statistics and running buffers are fp32 whatever the activations' dtype."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, slope):
+        c, rows = x.shape[-1], ops.rows_of(x)
+        if training and rows <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        rm32 = rv32 = None
+        if running_mean is not None:  # (a bf16 module's buffers: an fp32 round trip around the kernel)
+            rm32 = running_mean if running_mean.dtype == torch.float32 else running_mean.float()
+            rv32 = running_var if running_var.dtype == torch.float32 else running_var.float()
+        elif not training:
+            raise ValueError("batch_norm_act: eval mode needs the running buffers")
+        stats = ops.channel_stats(x) if training else None
+        scale, shift, mean, invstd = ops.bn_finalize(stats, rows, c, ops.as_f32(gamma), ops.as_f32(beta), rm32, rv32, training, momentum, eps)
+        if training and rm32 is not None and rm32 is not running_mean:
+            running_mean.copy_(rm32)
+            running_var.copy_(rv32)
+        y = ops.bn_apply(x, scale, shift, slope)
+        ctx.save_for_backward(x, scale, shift, mean, invstd)
+        ctx.cfg = (bool(training), slope)
+        ctx.dtypes = (None if gamma is None else gamma.dtype, None if beta is None else beta.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, scale, shift, mean, invstd = ctx.saved_tensors
+        training, slope = ctx.cfg
+        want = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dx, dgamma, dbeta = ops.bn_backward(x, gy.contiguous(), scale, shift, mean, invstd, training, slope, want_affine_grads=want)
+        dgamma = dgamma.to(ctx.dtypes[0]) if ctx.needs_input_grad[1] else None
+        dbeta = dbeta.to(ctx.dtypes[1]) if ctx.needs_input_grad[2] else None
+        return dx, dgamma, dbeta, None, None, None, None, None, None
+
+
+def batch_norm_act(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], running_mean: Optional[torch.Tensor],
+                   running_var: Optional[torch.Tensor], training: bool, momentum: float, eps: float, slope: Optional[float]) -> torch.Tensor:
+    """LeakyReLU_slope(F.batch_norm(x, running_mean, running_var, gamma, beta, training, momentum, eps)) over an arena tensor; differentiable in x, gamma
+    and beta.  training: batch statistics, and the running buffers are updated in place (also under torch.no_grad()); eval: the running buffers."""
+    return _BatchNormAct.apply(x, gamma, beta, running_mean, running_var, bool(training), float(momentum), float(eps), None if slope is None else float(slope))
+
+
+class _AvgPool(torch.autograd.Function):
+    """nn.AvgPool{2,3}d(kernel_size, stride 2, padding) of an arena tensor on the separable tap kernel; the gradient: the same kernel, transposed tables."""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan = plan
+        return ops.resize(x, plan.mode, plan=plan)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return ops.resize_backward(gy.contiguous(), ctx.plan), None
+
+
+def avg_pool(x: torch.Tensor, kernel_size: int, padding: int, count_include_pad: bool = True) -> torch.Tensor:
+    """F.avg_pool{2,3}d(x, kernel_size, stride=2, padding=padding, count_include_pad=...) of an arena tensor; differentiable in x."""
+    from .resize_plan import avg_pool_plan
+
+    return _AvgPool.apply(x, avg_pool_plan(tuple(x.shape[1:-1]), kernel_size, 2, padding, count_include_pad))
+
+
+class _PatchAdvLoss(torch.autograd.Function):
+    """One discriminator output through PatchAdversarialLoss (losses/adversarial_loss.py); the backward re-reads the logits and scales by the upstream
+    gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, x, criterion, target, activation, reduction):
+        ctx.save_for_backward(x)
+        ctx.cfg = (criterion, target, activation, reduction)
+        return ops.patch_adv_loss(x, criterion, target, activation, reduction)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        criterion, target, activation, reduction = ctx.cfg
+        up = g.contiguous() if reduction == "none" else g.to(torch.float32).contiguous()
+        dx = ops.patch_adv_loss(x, criterion, target, activation, reduction, upstream=up, want_value=False, want_grad=True)
+        return dx.reshape(x.shape), None, None, None, None
+
+
+def patch_adv_loss(x: torch.Tensor, criterion: str, target: float, activation: bool = True, reduction: str = "mean") -> torch.Tensor:
+    """The criterion ("bce", "hinge", "least_squares") of one discriminator output against a constant target, reduced to an fp32 scalar ("mean" / "sum") or
+    element-wise ("none"); differentiable in x."""
+    ops.require_device(x)
+    return _PatchAdvLoss.apply(x, criterion, float(target), bool(activation), reduction)

@@ -718,6 +718,139 @@ def kld(mu: torch.Tensor, logvar: torch.Tensor, upstream: Optional[torch.Tensor]
     return (dmu, dlv) if not want_value else (value, dmu, dlv)
 
 
+# ---- BatchNorm (+ LeakyReLU): csrc/batchnorm.hip.  Every table is fp32 [C]; the statistics run over all rows of the arena tensor (batch and space). -------
+BN_ACT = {"none": 0, "leakyrelu": 1}
+
+
+def _bn_act(slope: Optional[float]):
+    if slope is not None and slope < 0:
+        raise ValueError("BatchNorm + LeakyReLU: the backward re-makes the sign from the pre-activation, slope >= 0")
+    return (BN_ACT["none"], 0.0) if slope is None else (BN_ACT["leakyrelu"], float(slope))
+
+
+def _bn_table(t: Optional[torch.Tensor], c: int, what: str) -> None:
+    if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (c,) or not t.is_contiguous()):
+        raise ValueError(f"batch norm: {what} must be a contiguous fp32 [{c}] tensor")
+
+
+def bn_finalize(stats: Optional[torch.Tensor], rows: int, c: int, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor],
+                running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], training: bool, momentum: float, eps: float):
+    """The per-channel tables of one BatchNorm call -> fp32 [C] (scale, shift, mean, invstd).  training: from the [S, N, C, 2] fp64 partials of
+    ops.channel_stats over `rows` = N * V rows, and the running buffers (fp32, may be None) are updated in place; eval: from the running buffers."""
+    require_device(stats, gamma, beta, running_mean, running_var)
+    for t, what in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _bn_table(t, c, what)
+    if training:
+        if stats is None or stats.dtype != torch.float64 or stats.dim() != 4 or stats.shape[2] != c or stats.shape[3] != 2 or not stats.is_contiguous():
+            raise ValueError("bn_finalize: training needs the [S, N, C, 2] fp64 statistic partials")
+        s_, n = stats.shape[0], stats.shape[1]
+        if n == 0 or rows % n:
+            raise ValueError("bn_finalize: rows must be N * V")
+        v = rows // n
+        device = stats.device
+    else:
+        if running_mean is None or running_var is None:
+            raise ValueError("bn_finalize: eval needs the running buffers")
+        s_, n, v = 0, 0, 0
+        device = running_mean.device
+    out = torch.empty((4, c), dtype=torch.float32, device=device)
+    if c == 0:  # no channels: nothing to launch (an empty tensor has no pointer to hand to the library)
+        return out[0], out[1], out[2], out[3]
+    check(lib().gm_bn_finalize(_ptr(stats) if training else None, s_, n, c, v, _ptr(gamma), _ptr(beta), float(eps), float(momentum), int(bool(training)),
+                               _ptr(running_mean), _ptr(running_var), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), _stream()),
+          "gm_bn_finalize")
+    return out[0], out[1], out[2], out[3]
+
+
+def bn_apply(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, slope: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LeakyReLU_slope(x * scale[c] + shift[c]) (slope None: no activation) in one pass over an arena tensor; x / out may be channel slices."""
+    require_device(x, scale, shift, out)
+    c = x.shape[-1]
+    _bn_table(scale, c, "scale")
+    _bn_table(shift, c, "shift")
+    act, sl = _bn_act(slope)
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    elif out.shape != x.shape or out.dtype != x.dtype:
+        raise ValueError("bn_apply: out must match x")
+    _timed(f"bn_apply<{str(x.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float(2 * x.element_size() * x.numel()), shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_bn_apply(x.data_ptr(), arena_ld(x), out.data_ptr(), arena_ld(out), scale.data_ptr(), shift.data_ptr(), rows_of(x), c, act, sl,
+                                           dt_code(x.dtype), _stream()), "gm_bn_apply"))
+    return out
+
+
+def bn_backward(x: torch.Tensor, gy: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, training: bool,
+                slope: Optional[float] = None, want_affine_grads: bool = True):
+    """Backward of y = LeakyReLU_slope(BatchNorm(x)) from the forward call's own tables: -> (dx, dgamma, dbeta), the parameter gradients fp32 [C] (None when
+    not requested).  Three launches: the {sum g, sum g xhat} partials, their fixed-order fold, the apply pass."""
+    require_device(x, gy, scale, shift, mean, invstd)
+    if gy.shape != x.shape or gy.dtype != x.dtype:
+        raise ValueError("bn_backward: gy must match x")
+    c, rows = x.shape[-1], rows_of(x)
+    for t, what in ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd")):
+        _bn_table(t, c, what)
+    act, sl = _bn_act(slope)
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    dgamma = torch.zeros(c, dtype=torch.float32, device=x.device) if want_affine_grads else None
+    dbeta = torch.zeros(c, dtype=torch.float32, device=x.device) if want_affine_grads else None
+    if x.numel() == 0:
+        return dx, dgamma, dbeta
+    name, nbytes = str(x.dtype).split(".")[-1], float(x.element_size() * x.numel())
+    slots = int(lib().gm_bn_bwd_stats_slots(rows))
+    part = torch.empty((slots, c, 2), dtype=torch.float64, device=x.device)  # one stored partial per (row block, channel): nothing to zero
+    _timed(f"bn_bwd_stats<{name}>", dict(flops=0.0, bytes=2 * nbytes, shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_bn_bwd_stats(x.data_ptr(), arena_ld(x), gy.data_ptr(), arena_ld(gy), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
+                                               invstd.data_ptr(), rows, c, act, sl, part.data_ptr(), dt_code(x.dtype), _stream()), "gm_bn_bwd_stats"))
+    coef = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    check(lib().gm_bn_bwd_finalize(part.data_ptr(), slots, c, rows, scale.data_ptr(), invstd.data_ptr(), int(bool(training)), _ptr(dgamma), _ptr(dbeta),
+                                   coef[0].data_ptr(), coef[1].data_ptr(), _stream()), "gm_bn_bwd_finalize")
+    _timed(f"bn_bwd_apply<{name}>", dict(flops=0.0, bytes=3 * nbytes, shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_bn_bwd_apply(x.data_ptr(), arena_ld(x), gy.data_ptr(), arena_ld(gy), dx.data_ptr(), arena_ld(dx), scale.data_ptr(),
+                                               shift.data_ptr(), mean.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), rows, c, act, sl, dt_code(x.dtype),
+                                               _stream()), "gm_bn_bwd_apply"))
+    return dx, dgamma, dbeta
+
+
+ADV_CRITERION = {"bce": 0, "hinge": 1, "least_squares": 2}
+
+
+def patch_adv_loss(x: torch.Tensor, criterion: str, target: float, activation: bool = True, reduction: str = "mean", upstream: Optional[torch.Tensor] = None,
+                   want_value: bool = True, want_grad: bool = False):
+    """One discriminator output through PatchAdversarialLoss's activation, criterion and reduction (gm_patch_adv_loss: one work-group, fp64, fixed order).
+    criterion "bce" / "least_squares": target = the label; "hinge": target = +1 (real) / -1 (fake).  reduction "mean" / "sum": an fp32 scalar;
+    "none": the element-wise terms in the dtype and shape of x.  want_grad: the gradient with respect to x, scaled by `upstream` (an fp32 scalar
+    tensor for "mean" / "sum", a map like x for "none"; None: 1).  -> value, grad, or (value, grad)."""
+    require_device(x, upstream)
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"patch_adv_loss: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    if not (want_value or want_grad):
+        raise ValueError("patch_adv_loss: nothing asked for")
+    x = x.contiguous()
+    total = x.numel()
+    elementwise = reduction == "none"
+    if upstream is not None:
+        if elementwise and (upstream.shape != x.shape or upstream.dtype != x.dtype):
+            raise ValueError("patch_adv_loss: the upstream gradient of reduction 'none' is a map like x")
+        if not elementwise and (upstream.numel() != 1 or upstream.dtype != torch.float32):
+            raise ValueError("patch_adv_loss: the upstream gradient is one fp32 value")
+        upstream = upstream.contiguous()
+    value = elem = None
+    if want_value:
+        if elementwise:
+            value = elem = torch.empty_like(x)
+        else:
+            value = torch.empty((), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if want_grad else None
+    if total == 0 and (elementwise or not want_value):
+        return (value, dx) if want_value and want_grad else (value if want_value else dx)
+    out_scale = 1.0 / total if reduction == "mean" and total else 1.0
+    _timed(f"patch_adv_loss<{str(x.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float(x.element_size() * total), shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_patch_adv_loss(x.data_ptr(), total, ADV_CRITERION[criterion], int(bool(activation)), float(target), out_scale,
+                                                 None if elementwise else _ptr(value), _ptr(elem), None if elementwise else _ptr(upstream),
+                                                 _ptr(upstream) if elementwise else None, _ptr(dx), dt_code(x.dtype), _stream()), "gm_patch_adv_loss"))
+    return (value, dx) if want_value and want_grad else (value if want_value else dx)
+
+
 class VirtualCat:
     """Channel concatenation that is never materialised (reference: torch.cat([h, skip], dim=1), diffusion_model_unet.py:1232,
     1340,1461): its consumers read the parts directly."""

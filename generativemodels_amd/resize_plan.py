@@ -25,7 +25,7 @@ from typing import Optional, Sequence, Union
 
 import numpy as np
 
-__all__ = ["axis_taps", "ResizePlan", "plan_for", "MODES"]
+__all__ = ["axis_taps", "avg_pool_taps", "ResizePlan", "plan_for", "avg_pool_plan", "MODES"]
 
 # mode -> (per-axis table kind, the spatial dimensionalities torch serves it for)
 MODES = {"nearest": ("nearest", (1, 2, 3)), "area": ("area", (1, 2, 3)), "linear": ("linear", (1,)), "bilinear": ("linear", (2,)),
@@ -75,6 +75,23 @@ def axis_taps(kind: str, n_in: int, n_out: int, scale_factor: Optional[float] = 
             t = src - _F(i)
             coef = (_cubic2(t + _F(1)), _cubic1(t), _cubic1(_F(1) - t), _cubic2(_F(2) - t))
             taps.append([(min(max(i - 1 + k, 0), n_in - 1), coef[k]) for k in range(4)])
+    return taps
+
+
+def avg_pool_taps(n_in: int, kernel_size: int, stride: int, padding: int, count_include_pad: bool = True) -> list:
+    """nn.AvgPool{1,2,3}d (ceil_mode=False) along one axis -> per output index its (input index, fp32 weight) taps: the in-range inputs of the window
+    [o * stride - padding, + kernel_size), each weighted 1 / kernel_size (count_include_pad: the padding counts as zeros) or 1 / (in-range inputs).  The
+    N-D pooling is the product of its per-axis tables under either rule."""
+    if kernel_size < 1 or stride < 1 or padding < 0 or 2 * padding > kernel_size:
+        raise ValueError(f"avg_pool: kernel_size {kernel_size}, stride {stride}, padding {padding} (padding is at most half the kernel size)")
+    n_out = (n_in + 2 * padding - kernel_size) // stride + 1
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"avg_pool: an axis of {n_in} is too short for kernel_size {kernel_size} with padding {padding}")
+    taps = []
+    for o in range(n_out):
+        lo, hi = max(o * stride - padding, 0), min(o * stride - padding + kernel_size, n_in)
+        w = _F(1) / _F(kernel_size if count_include_pad else hi - lo)
+        taps.append([(i, w) for i in range(lo, hi)])
     return taps
 
 
@@ -143,6 +160,25 @@ class ResizePlan:
         self._device: dict = {}
         self.launch_cache: dict = {}  # what the launcher derives from the device tables (its descriptor), per (device, direction)
 
+    @classmethod
+    def from_taps(cls, mode: str, in_spatial: Sequence[int], taps: Sequence[list]) -> "ResizePlan":
+        """A plan from explicit per-axis tap tables (taps[a][o] = the (input index, weight) list of output o along spatial axis a): any separable linear map
+        the kernel can run that F.interpolate does not express -- `mode` only names it.  An output without taps is zero."""
+        in_spatial = tuple(int(v) for v in in_spatial)
+        if not 1 <= len(in_spatial) <= 3 or len(taps) != len(in_spatial):
+            raise ValueError(f"resize: {len(taps)} tap tables for spatial extents {in_spatial} (1 to 3 axes, one table each)")
+        for n, axis in zip(in_spatial, taps):
+            if n < 1 or len(axis) < 1 or any(not 0 <= int(i) < n for t in axis for i, _ in t):
+                raise ValueError("resize: a tap table needs at least one output and input indices inside its axis")
+        plan = cls.__new__(cls)
+        plan.mode, plan.in_spatial, plan.out_spatial = mode, in_spatial, tuple(len(axis) for axis in taps)
+        plan.tables = tuple(_csr(axis) for axis in taps)
+        plan.max_taps = _max_taps(plan.tables)
+        plan._transposed = plan._max_taps_transposed = None
+        plan._device = {}
+        plan.launch_cache = {}
+        return plan
+
     @property
     def transposed(self) -> tuple:
         if self._transposed is None:
@@ -194,4 +230,16 @@ def plan_for(mode: str, in_spatial: Sequence[int], size=None, scale_factor=None)
         if len(_PLANS) > 4096:
             _PLANS.clear()
         plan = _PLANS[key] = ResizePlan(mode, in_spatial, size, scale_factor)
+    return plan
+
+
+def avg_pool_plan(in_spatial: Sequence[int], kernel_size: int, stride: int, padding: int, count_include_pad: bool = True) -> ResizePlan:
+    """The cached plan of nn.AvgPool{1,2,3}d(kernel_size, stride, padding, count_include_pad=...) (the same value on every axis) over `in_spatial`."""
+    in_spatial = tuple(int(v) for v in in_spatial)
+    key = ("avg_pool", in_spatial, int(kernel_size), int(stride), int(padding), bool(count_include_pad))
+    plan = _PLANS.get(key)
+    if plan is None:
+        if len(_PLANS) > 4096:
+            _PLANS.clear()
+        plan = _PLANS[key] = ResizePlan.from_taps("avg_pool", in_spatial, [avg_pool_taps(n, kernel_size, stride, padding, count_include_pad) for n in in_spatial])
     return plan

@@ -647,6 +647,41 @@ int gm_spectral_loss_partials(long long bins);
 int gm_spectral_loss(const float* x, const float* y, long long batch, int m0, int m1, int m2, int n_last, const float* upstream, float* hx, float* hy,
                      float* full, double* partials, float* out, double out_scale, void* stream);
 
+/* ---- BatchNorm (+ LeakyReLU) over arena tensors (networks/nets/patchgan_discriminator.py) ----------------------------------------------
+ * Operands are [rows][C] with a row pitch in elements, rows = N * V: the statistics run over the batch and every spatial position, so every table is
+ * per channel ([C] fp32).  act: 0 none, 1 LeakyReLU with `slope` >= 0 (ReLU is slope 0).  No atomics: every sum is a fixed-order fold.
+ * gm_bn_finalize: training != 0 folds the [S][N][C][2] fp64 (sum, sum of squares) partials over S and N and writes scale = gamma * invstd,
+ * shift = beta - mean * scale (biased variance; gamma / beta NULL: 1 / 0), mean and invstd (either may be NULL), and updates the running buffers in
+ * place (NULL: not tracked): r <- (1 - momentum) * r + momentum * stat, the variance unbiased (n / (n - 1), n = N * V).  training == 0: scale / shift (and
+ * mean / invstd when given) from the running buffers, which are left alone. */
+int gm_bn_finalize(const double* stats, int S, int N, int C, long long V, const float* gamma, const float* beta, float eps, float momentum, int training,
+                   float* running_mean, float* running_var, float* scale, float* shift, float* mean, float* invstd, void* stream);
+/* y = act(x * scale[c] + shift[c]), rounded once */
+int gm_bn_apply(const void* x, long long x_ld, void* y, long long y_ld, const float* scale, const float* shift, long long rows, int C, int act, float slope,
+                int dtype, void* stream);
+/* out[slot][c] = {sum g, sum g * xhat} (fp64) over the rows of block `slot`, g = gy * act'(x * scale + shift), xhat = (x - mean) * invstd; each of the
+ * gm_bn_bwd_stats_slots(rows) x C partials is stored exactly once */
+long long gm_bn_bwd_stats_slots(long long rows);
+int gm_bn_bwd_stats(const void* x, long long x_ld, const void* gy, long long gy_ld, const float* scale, const float* shift, const float* mean,
+                    const float* invstd, long long rows, int C, int act, float slope, double* out, int dtype, void* stream);
+/* the fold of those partials: dgamma = sum g * xhat, dbeta = sum g (either may be NULL), and the coefficient tables of gm_bn_bwd_apply:
+ * training != 0   cb = -scale * invstd * mean_rows(g * xhat), cc = -scale * mean_rows(g);   training == 0   cb = cc = 0 (the statistics are constants) */
+int gm_bn_bwd_finalize(const double* partials, int slots, int C, long long rows, const float* scale, const float* invstd, int training, float* dgamma,
+                       float* dbeta, float* cb, float* cc, void* stream);
+/* dx = g * scale + (x - mean) * cb + cc  =  gamma * invstd * (g - mean_rows(g) - xhat * mean_rows(g * xhat)) in training, g * scale in eval */
+int gm_bn_bwd_apply(const void* x, long long x_ld, const void* gy, long long gy_ld, void* dx, long long dx_ld, const float* scale, const float* shift,
+                    const float* mean, const float* cb, const float* cc, long long rows, int C, int act, float slope, int dtype, void* stream);
+
+/* ---- PatchAdversarialLoss over one discriminator output (losses/adversarial_loss.py) ----------------------------------------------------
+ * Per logit x: criterion 0 bce  -(t max(log s, -100) + (1 - t) max(log(1 - s), -100)), s = sigmoid(x);  1 hinge  -min(t tanh(x) - 1, 0), t = +1 / -1;
+ * 2 least squares  (a - t)^2, a = LeakyReLU_0.05(x) (act != 0) or x.  One work-group, fp64, fixed order.
+ *   out (fp32, may be NULL)   out_scale * the sum of the terms (out_scale = 1 / total: the mean)
+ *   elem (may be NULL)        the terms themselves, in the dtype of x
+ *   dx (may be NULL)          the derivative of the terms with respect to x, times out_scale * upstream[0] (upstream NULL: 1), or -- with
+ *                             upstream_elem, a map in the dtype of x -- times upstream_elem[i] alone */
+int gm_patch_adv_loss(const void* x, long long total, int criterion, int act, float target, double out_scale, float* out, void* elem, const float* upstream,
+                      const void* upstream_elem, void* dx, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
