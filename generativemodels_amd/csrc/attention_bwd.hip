@@ -11,23 +11,55 @@
 // means every operand -- K^T, Q^T, dO^T included -- is read from a natural [row][channel] tile with no transposed staging.  That is
 // 1/8 of the bf16 MFMA rate: right for the latent-resolution attention of a training step (C4: 512-4096 tokens), and what makes a
 // 32768-token backward possible at all; a bf16 version needs transposed K / Q / dO images (ds_read_b64_tr_b16) and is the follow-up.
-#include "attn_bwd_tiles.h"  // ab_load4 / ab_store4 / ab_stage / ab_load_own / ab_rows_dot / ab_cols_acc, shared with attention_bwd_causal.hip
+//
+// CAUSAL compiles the forward's mask in (GmAttnDesc.causal: query i sees keys j <= i + off, off = Lk - Lq >= 0; reference: torch autograd through
+// blocks/selfattention.py:117-147 with its lower-triangular mask -- what a training step of the DecoderOnlyTransformer differentiates).  It changes
+// two things and nothing else:
+//   * the mask: one predicate, ab_visible, and one form -- a masked probability is EXACTLY 0, by a select (`ok ? expf(...) : 0.f`), never by
+//     arithmetic on infinities.  Without the mask the predicate only cuts the rows past either sequence -- and attn_bwd_dkv_kernel, alone, cuts
+//     its streamed rows with an infinite log-sum-exp in LDS instead, because the per-entry test costs it 1 - 4 % (the note at ldsL).
+//   * the walk: a work-group streams only the tiles that hold a visible (query, key) pair for its own rows (attn_bwd_causal_walk.h; bounds from
+//     blockIdx alone, because the loop body synchronises the work-group): key tiles [0, key_end) for own queries, query tiles [query_begin, Lq)
+//     for own keys.  About half the tiles of a square problem.  (The forward keeps no log-sum-exp for causal launches -- attention_dma.hip declines
+//     them -- so the pre sweep always runs.)
+#include "attn_bwd_tiles.h"  // AB_ROWS / AB_OWN, ab_load4 / ab_store4 / ab_stage / ab_load_own / ab_rows_dot / ab_cols_acc
+#include "attn_bwd_causal_walk.h"
 
-// ---- LSE and Dsum ---------------------------------------------------------------------------------------------------------------
-template <typename T, int DH>
+static_assert(ABC_TILE == AB_ROWS && ABC_OWN == AB_OWN, "the walk's tile and block are the streamed tile and the own rows of attn_bwd_tiles.h");
+
+// Does the pair (query, key) carry probability?  own_ok: the work-group's own row lies inside its sequence; row < rows: so does the streamed
+// tile's row; off = Lk - Lq.
+template <bool CAUSAL>
+__device__ __forceinline__ bool ab_visible(bool own_ok, int row, int rows, int query, int key, int off) {
+  return own_ok && row < rows && (!CAUSAL || key <= query + off);
+}
+
+// a * b rounded to fp32 on its own, never fused into an addition that follows
+__device__ __forceinline__ float ab_mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// ---- LSE over the visible keys and Dsum -----------------------------------------------------------------------------------------
+template <typename T, int DH, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(const GmAttnBwdDesc p, float* __restrict__ lse, float* __restrict__ dsum) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ldsK = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, qg = lane >> 4;
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
-  const int my_q = blockIdx.x * ((int)blockDim.x >> 2) + wave * 16 + l15;
+  const int off = p.Lk - p.Lq;
+  const int my_q = blockIdx.x * AB_OWN + wave * 16 + l15;
   const bool q_ok = my_q < p.Lq;
   const T* Qb = reinterpret_cast<const T*>(p.q) + (long long)b * p.Lq * p.q_ld + h * p.dh;
   const T* Kb = reinterpret_cast<const T*>(p.k) + (long long)b * p.Lk * p.k_ld + h * p.dh;
   float4 qf[DH / 16];
   ab_load_own<T, DH>(Qb + (long long)(q_ok ? my_q : 0) * p.q_ld, q_ok, qf, qg);
+  // Key 0 is visible to every query (under the mask because off >= 0) and lies in the first tile, and the tile maximum below is taken over the four lanes of a query:
+  // m_run is finite after the first tile, so exp(m_run - m_new) never sees inf - inf.  (Before it, l_run = 0 and exp(-inf - finite) = 0.)  Own rows
+  // past the sequence hold a zero query and are not stored; they stay visible here (own_ok = true) so that the same holds for them.
   float m_run = -INFINITY, l_run = 0.f;
-  for (int key0 = 0; key0 < p.Lk; key0 += AB_ROWS) {
+  const int key_end = CAUSAL ? abc_key_end(p.Lq, p.Lk, blockIdx.x) : p.Lk;  // uniform over the work-group
+  for (int key0 = 0; key0 < key_end; key0 += AB_ROWS) {
     __syncthreads();
     ab_stage<T, DH>(Kb, p.k_ld, key0, p.Lk, ldsK, tid);
     __syncthreads();
@@ -38,9 +70,12 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(const GmAttnBwdDesc p
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float sv = key0 + f * 16 + qg * 4 + r < p.Lk ? s[f][r] * p.scale : -INFINITY;
-        s[f][r] = sv;
-        tmax = fmaxf(tmax, sv);
+        const int key = key0 + f * 16 + qg * 4 + r;
+        // The one place the two forms differ in arithmetic: under the mask scale * s fuses with the subtraction of the maximum below (one fma);
+        // without it the product has always been rounded first.  The log-sum-exp of either keeps its bits (an exact scale, dh = 16 / 64 / 256,
+        // shows no difference).
+        s[f][r] = CAUSAL ? s[f][r] * p.scale : ab_mul_rounded(s[f][r], p.scale);
+        if (ab_visible<CAUSAL>(true, key, p.Lk, my_q, key, off)) tmax = fmaxf(tmax, s[f][r]);
       }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -49,7 +84,10 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(const GmAttnBwdDesc p
 #pragma unroll
     for (int f = 0; f < 2; ++f)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) psum += expf(s[f][r] - m_new);
+      for (int r = 0; r < 4; ++r) {
+        const int key = key0 + f * 16 + qg * 4 + r;
+        psum += ab_visible<CAUSAL>(true, key, p.Lk, my_q, key, off) ? expf(s[f][r] - m_new) : 0.f;
+      }
     l_run = l_run * expf(m_run - m_new) + psum;
     m_run = m_new;
   }
@@ -76,7 +114,7 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(const GmAttnBwdDesc p
 
 // ---- dQ ---------------------------------------------------------------------------------------------------------------------------
 // CS: the head dim is covered in CS channel slices (blockIdx.z) of DH / CS accumulated channels each (register budget at d = 256)
-template <typename T, int DH, int CS>
+template <typename T, int DH, int CS, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const GmAttnBwdDesc p, const float* __restrict__ lse, const float* __restrict__ dsum) {
   constexpr int DF = DH / CS / 16, PITCH = DH + 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -85,7 +123,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const GmAttnBwdDesc p,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, qg = lane >> 4;
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
   const int c0 = blockIdx.z * (DH / CS);
-  const int my_q = blockIdx.x * ((int)blockDim.x >> 2) + wave * 16 + l15;
+  const int off = p.Lk - p.Lq;
+  const int my_q = blockIdx.x * AB_OWN + wave * 16 + l15;
   const bool q_ok = my_q < p.Lq;
   const long long qrow = (long long)b * p.Lq + (q_ok ? my_q : 0);
   const T* Kb = reinterpret_cast<const T*>(p.k) + (long long)b * p.Lk * p.k_ld + h * p.dh;
@@ -98,7 +137,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const GmAttnBwdDesc p,
   f32x4_t acc[DF];
 #pragma unroll
   for (int d = 0; d < DF; ++d) acc[d] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  for (int key0 = 0; key0 < p.Lk; key0 += AB_ROWS) {
+  const int key_end = CAUSAL ? abc_key_end(p.Lq, p.Lk, blockIdx.x) : p.Lk;  // uniform over the work-group
+  for (int key0 = 0; key0 < key_end; key0 += AB_ROWS) {
     __syncthreads();
     ab_stage<T, DH>(Kb, p.k_ld, key0, p.Lk, ldsK, tid);
     ab_stage<T, DH>(Vb, p.v_ld, key0, p.Lk, ldsV, tid);
@@ -110,7 +150,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const GmAttnBwdDesc p,
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const bool ok = key0 + f * 16 + qg * 4 + r < p.Lk;
+        const int key = key0 + f * 16 + qg * 4 + r;
+        const bool ok = ab_visible<CAUSAL>(q_ok, key, p.Lk, my_q, key, off);
         const float pr = ok ? expf(s[f][r] * p.scale - my_lse) : 0.f;
         s[f][r] = pr * (dp[f][r] - my_d) * p.scale;  // dS^T
       }
@@ -123,7 +164,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const GmAttnBwdDesc p,
 }
 
 // ---- dK, dV ---------------------------------------------------------------------------------------------------------------------
-template <typename T, int DH, int CS>
+template <typename T, int DH, int CS, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const GmAttnBwdDesc p, const float* __restrict__ lse, const float* __restrict__ dsum) {
   constexpr int DF = DH / CS / 16, PITCH = DH + 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -133,7 +174,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const GmAttnBwdDesc p
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, qg = lane >> 4;
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
   const int c0 = blockIdx.z * (DH / CS);
-  const int my_k = blockIdx.x * ((int)blockDim.x >> 2) + wave * 16 + l15;
+  const int off = p.Lk - p.Lq;
+  const int my_k = blockIdx.x * AB_OWN + wave * 16 + l15;
   const bool k_ok = my_k < p.Lk;
   const long long krow = (long long)b * p.Lk + (k_ok ? my_k : 0);
   const T* Qb = reinterpret_cast<const T*>(p.q) + (long long)b * p.Lq * p.q_ld + h * p.dh;
@@ -144,13 +186,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const GmAttnBwdDesc p
   f32x4_t dka[DF], dva[DF];
 #pragma unroll
   for (int d = 0; d < DF; ++d) { dka[d] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dva[d] = dka[d]; }
-  for (int q0 = 0; q0 < p.Lq; q0 += AB_ROWS) {
+  const int q_begin = CAUSAL ? abc_query_begin(p.Lq, p.Lk, blockIdx.x) : 0;  // uniform over the work-group
+  for (int q0 = q_begin; q0 < p.Lq; q0 += AB_ROWS) {
     __syncthreads();
     ab_stage<T, DH>(Qb, p.q_ld, q0, p.Lq, ldsQ, tid);
     ab_stage<T, DH>(Gb, p.go_ld, q0, p.Lq, ldsG, tid);
     if (tid < AB_ROWS) {
+      // Rows past the sequence: under the mask ab_visible cuts them below and their entries only have to be finite.  Without the mask that
+      // per-entry test is all the predicate would add, and it costs this kernel 1 - 4 % (measured at 512 and 4096 tokens, d = 128): there the
+      // row's log-sum-exp is infinite instead, exp(s - inf) = 0, and the select below only looks at the own row.
       const bool ok = q0 + tid < p.Lq;
-      ldsL[tid] = ok ? lse[(long long)bh * p.Lq + q0 + tid] : INFINITY;  // exp(s - inf) = 0: rows past the sequence contribute nothing
+      ldsL[tid] = ok ? lse[(long long)bh * p.Lq + q0 + tid] : CAUSAL ? 0.f : INFINITY;
       ldsL[AB_ROWS + tid] = ok ? dsum[(long long)bh * p.Lq + q0 + tid] : 0.f;
     }
     __syncthreads();
@@ -162,8 +208,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const GmAttnBwdDesc p
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = f * 16 + qg * 4 + r;
-        const float pr = k_ok ? expf(s[f][r] * p.scale - ldsL[row]) : 0.f;
+        const int row = f * 16 + qg * 4 + r, qi = q0 + row;
+        const bool ok = CAUSAL ? ab_visible<CAUSAL>(k_ok, qi, p.Lq, qi, my_k, off) : k_ok;
+        const float pr = ok ? expf(s[f][r] * p.scale - ldsL[row]) : 0.f;
         pm[f][r] = pr;
         s[f][r] = pr * (dp[f][r] - ldsL[AB_ROWS + row]) * p.scale;  // dS
       }
@@ -181,10 +228,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const GmAttnBwdDesc p
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-extern "C" long long gm_attention_backward_workspace_bytes(const GmAttnBwdDesc* d) {
-  if (!d) return -1;
-  return 2LL * d->B * d->H * d->Lq * (long long)sizeof(float);
+// block: index of a 64-row work-group on either side.  key_end: the key tiles [0, key_end) the work-group owning queries [64 block, ...) streams
+// (0 when it owns no query); query_begin: the query tiles [query_begin, Lq) the work-group owning keys [64 block, ...) streams (Lq when it owns
+// no key).  Pure host arithmetic over attn_bwd_causal_walk.h, the functions the kernels call; -1 (and no error text, like the other planners) for
+// arguments outside 0 < Lq <= Lk, 0 <= block.
+extern "C" int gm_attention_backward_causal_walk(int Lq, int Lk, int block, int* key_end, int* query_begin) {
+  if (!key_end || !query_begin || Lq <= 0 || Lk < Lq || block < 0 || block > (1 << 24)) return -1;
+  *key_end = (long long)ABC_OWN * block < Lq ? abc_key_end(Lq, Lk, block) : 0;
+  *query_begin = (long long)ABC_OWN * block < Lk ? abc_query_begin(Lq, Lk, block) : Lq;
+  return 0;
 }
+
+static long long ab_workspace_bytes(const GmAttnBwdDesc* d) {
+  if (!d) return -1;
+  return 2LL * d->B * d->H * d->Lq * (long long)sizeof(float);  // LSE and dO.O per query
+}
+extern "C" long long gm_attention_backward_workspace_bytes(const GmAttnBwdDesc* d) { return ab_workspace_bytes(d); }
+extern "C" long long gm_attention_backward_causal_workspace_bytes(const GmAttnBwdDesc* d) { return ab_workspace_bytes(d); }
 
 template <typename KernT>
 static void ab_set_lds(KernT kern) {
@@ -192,62 +252,85 @@ static void ab_set_lds(KernT kern) {
   if (e != hipSuccess) (void)hipGetLastError();
 }
 
-template <typename T, int DH, int CS>
+template <typename T, int DH, int CS, bool CAUSAL>
 static void launch_attn_bwd(const GmAttnBwdDesc& d, hipStream_t st) {
   float* lse = reinterpret_cast<float*>(d.workspace);
   float* dsum = lse + (long long)d.B * d.H * d.Lq;
   constexpr size_t tile = (size_t)AB_ROWS * (DH + 4) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    ab_set_lds(attn_bwd_pre_kernel<T, DH>);
-    ab_set_lds(attn_bwd_dq_kernel<T, DH, CS>);
-    ab_set_lds(attn_bwd_dkv_kernel<T, DH, CS>);
+    ab_set_lds(attn_bwd_pre_kernel<T, DH, CAUSAL>);
+    ab_set_lds(attn_bwd_dq_kernel<T, DH, CS, CAUSAL>);
+    ab_set_lds(attn_bwd_dkv_kernel<T, DH, CS, CAUSAL>);
     attr_set = true;
   }
-  // own rows per work-group: 64 (4 waves share every streamed tile).  Measured at L = 4096, d = 128, one head (64 work-groups on 256
+  // own rows per work-group: AB_OWN = 64 (4 waves share every streamed tile).  Measured at L = 4096, d = 128, one head (64 work-groups on 256
   // CUs): one-wave work-groups (256 of them) were 2x SLOWER -- a lone wave staging whole tiles costs more than the idle CUs; short
   // single-head problems are better served by the composed backward (autograd.py), long or multi-head ones fill the chip anyway.
-  auto waves = [&](int, int) { return 4; };
-  const int wq0 = waves(d.Lq, 1), wq = waves(d.Lq, CS), wk = waves(d.Lk, CS);
-  attn_bwd_pre_kernel<T, DH><<<dim3((d.Lq + 16 * wq0 - 1) / (16 * wq0), d.B * d.H), 64 * wq0, tile, st>>>(d, lse, dsum);
-  attn_bwd_dq_kernel<T, DH, CS><<<dim3((d.Lq + 16 * wq - 1) / (16 * wq), d.B * d.H, CS), 64 * wq, 2 * tile, st>>>(d, lse, dsum);
-  attn_bwd_dkv_kernel<T, DH, CS><<<dim3((d.Lk + 16 * wk - 1) / (16 * wk), d.B * d.H, CS), 64 * wk, 2 * tile + 2 * AB_ROWS * sizeof(float), st>>>(
-      d, lse, dsum);
+  const int qblocks = (d.Lq + AB_OWN - 1) / AB_OWN, kblocks = (d.Lk + AB_OWN - 1) / AB_OWN;
+  attn_bwd_pre_kernel<T, DH, CAUSAL><<<dim3(qblocks, d.B * d.H), 256, tile, st>>>(d, lse, dsum);
+  attn_bwd_dq_kernel<T, DH, CS, CAUSAL><<<dim3(qblocks, d.B * d.H, CS), 256, 2 * tile, st>>>(d, lse, dsum);
+  attn_bwd_dkv_kernel<T, DH, CS, CAUSAL><<<dim3(kblocks, d.B * d.H, CS), 256, 2 * tile + 2 * AB_ROWS * sizeof(float), st>>>(d, lse, dsum);
 }
 
-template <typename T>
+template <typename T, bool CAUSAL>
 static int dispatch_attn_bwd(const GmAttnBwdDesc& d, hipStream_t st) {
   switch (d.dh) {
-    case 16: launch_attn_bwd<T, 16, 1>(d, st); return 0;
-    case 32: launch_attn_bwd<T, 32, 1>(d, st); return 0;
-    case 64: launch_attn_bwd<T, 64, 1>(d, st); return 0;
-    case 128: launch_attn_bwd<T, 128, 1>(d, st); return 0;
-    case 256: launch_attn_bwd<T, 256, 2>(d, st); return 0;
+    case 16: launch_attn_bwd<T, 16, 1, CAUSAL>(d, st); return 0;
+    case 32: launch_attn_bwd<T, 32, 1, CAUSAL>(d, st); return 0;
+    case 64: launch_attn_bwd<T, 64, 1, CAUSAL>(d, st); return 0;
+    case 128: launch_attn_bwd<T, 128, 1, CAUSAL>(d, st); return 0;
+    case 256: launch_attn_bwd<T, 256, 2, CAUSAL>(d, st); return 0;
     default: return -1;
   }
 }
 
-extern "C" int gm_attention_backward(const GmAttnBwdDesc* dp, void* stream) {
-  GM_REQUIRE(dp, "null descriptor");
+// What keeps the descriptor from being launched, as the first condition it misses; nullptr when nothing does.
+static const char* ab_refusal(const GmAttnBwdDesc* dp, bool causal) {
+  if (!dp) return "null descriptor";
   const GmAttnBwdDesc& d = *dp;
-  GM_REQUIRE(d.q && d.k && d.v && d.o && d.go && d.dq && d.dk && d.dv, "null tensor pointer");
-  GM_REQUIRE(d.B >= 0 && d.H > 0 && d.Lk > 0, "bad batch / head geometry");
-  GM_REQUIRE((long long)d.B * d.H <= 65535, "too many (batch, head) pairs for one launch");
-  GM_REQUIRE(d.workspace && d.workspace_bytes >= gm_attention_backward_workspace_bytes(dp), "workspace too small");
-  const int vec = d.dtype == GM_F32 ? 4 : 4;  // rows are read and written as 4-element vectors (16 / 8 bytes)
-  const int al = d.dtype == GM_F32 ? 16 : 8;
-  auto ok = [&](const void* p, long long ld) { return ld % vec == 0 && (reinterpret_cast<uintptr_t>(p) & (al - 1)) == 0; };
-  GM_REQUIRE(ok(d.q, d.q_ld) && ok(d.k, d.k_ld) && ok(d.v, d.v_ld) && ok(d.o, d.o_ld) && ok(d.go, d.go_ld) && ok(d.dq, d.dq_ld) &&
-                 ok(d.dk, d.dk_ld) && ok(d.dv, d.dv_ld), "operands must be 4-element aligned rows");
-  if (d.B == 0 || d.Lq == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (d.dtype == GM_F32) rc = dispatch_attn_bwd<float>(d, st);
-  else if (d.dtype == GM_BF16) rc = dispatch_attn_bwd<bf16_raw>(d, st);
-  else GM_FAIL(-2, "unsupported dtype");
+  if (!(d.q && d.k && d.v && d.o && d.go && d.dq && d.dk && d.dv)) return "null tensor pointer";
+  if (!(d.B >= 0 && d.H > 0 && d.Lk > 0 && (!causal || d.Lq >= 0))) return "bad batch / head geometry";
+  if (causal && d.Lk < d.Lq) return "causal attention needs at least as many keys as queries";
+  if ((long long)d.B * d.H > 65535) return "too many (batch, head) pairs for one launch";
+  if (!(d.workspace && d.workspace_bytes >= ab_workspace_bytes(dp))) return "workspace too small";
+  const int al = d.dtype == GM_F32 ? 16 : 8;  // rows are read and written as 4-element vectors (16 / 8 bytes)
+  auto ok = [&](const void* p, long long ld) { return ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & (al - 1)) == 0; };
+  if (!(ok(d.q, d.q_ld) && ok(d.k, d.k_ld) && ok(d.v, d.v_ld) && ok(d.o, d.o_ld) && ok(d.go, d.go_ld) && ok(d.dq, d.dq_ld) && ok(d.dk, d.dk_ld) &&
+        ok(d.dv, d.dv_ld)))
+    return "operands must be 4-element aligned rows";
+  return nullptr;
+}
+
+// Launches a non-empty descriptor ab_refusal passed.  0, or the code of the dtype (-2) / head dim (-1) no kernel is built for.
+template <bool CAUSAL>
+static int run_attn_bwd(const GmAttnBwdDesc& d, void* stream) {
+  if (d.dtype == GM_F32) return dispatch_attn_bwd<float, CAUSAL>(d, (hipStream_t)stream);
+  if (d.dtype == GM_BF16) return dispatch_attn_bwd<bf16_raw, CAUSAL>(d, (hipStream_t)stream);
+  return -2;
+}
+
+// (GM_FAIL records __func__: each entry point reports the shared answers under its own name)
+extern "C" int gm_attention_backward(const GmAttnBwdDesc* dp, void* stream) {
+  const char* refusal = ab_refusal(dp, false);
+  GM_REQUIRE(!refusal, refusal);
+  if (dp->B == 0 || dp->Lq == 0) return 0;
+  const int rc = run_attn_bwd<false>(*dp, stream);
+  if (rc == -2) GM_FAIL(-2, "unsupported dtype");
   GM_REQUIRE(rc == 0, "head dim must be 16, 32, 64, 128 or 256");
   GM_LAUNCH_CHECK();
 }
+
+extern "C" int gm_attention_backward_causal(const GmAttnBwdDesc* dp, void* stream) {
+  const char* refusal = ab_refusal(dp, true);
+  GM_REQUIRE(!refusal, refusal);
+  if (dp->B == 0 || dp->Lq == 0) return 0;
+  const int rc = run_attn_bwd<true>(*dp, stream);
+  if (rc == -2) GM_FAIL(-2, "unsupported dtype");
+  GM_REQUIRE(rc == 0, "head dim must be 16, 32, 64, 128 or 256");
+  GM_LAUNCH_CHECK();
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // bf16-MFMA score pass of the attention backward (round 3; VERDICT r2 "missing" #4).  The contractions of the backward come in two kinds:

@@ -1,4 +1,4 @@
-// Tile walk of the causal flash backward (attention_bwd_causal.hip).  Query i sees keys j <= i + off, off = Lk - Lq >= 0 (attn_common.h,
+// Tile walk of the causal flash backward (attention_bwd.hip, CAUSAL).  Query i sees keys j <= i + off, off = Lk - Lq >= 0 (attn_common.h,
 // GmAttnDesc.causal).  A work-group owns ABC_OWN consecutive rows and streams the other side in tiles of ABC_TILE rows with a
 // __syncthreads() per tile, so both bounds are functions of the work-group's block index alone -- never of a lane's own row.  The kernels and
 // the host entry point gm_attention_backward_causal_walk read the SAME two functions, so a host test checks the walk the kernels run.

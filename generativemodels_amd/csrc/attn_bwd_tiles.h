@@ -1,4 +1,4 @@
-// Device helpers of the fp32-MFMA flash backward kernels (attention_bwd.hip, attention_bwd_causal.hip): 4-element loads / stores in either storage
+// Device helpers of the fp32-MFMA flash backward kernels (attention_bwd.hip, with and without the causal mask): 4-element loads / stores in either storage
 // dtype, the staging of a 32-row streamed tile as fp32 into LDS, and the two MFMA contractions over it (tile rows x own rows, tile columns
 // accumulated into own rows).  The work-group's OWN rows are MFMA columns, one per lane (attention_bwd.hip's header comment).
 #pragma once
@@ -17,6 +17,7 @@ template <> __device__ __forceinline__ void ab_store4<bf16_raw>(bf16_raw* p, flo
 }
 
 #define AB_ROWS 32  // rows of a streamed tile (two 16-row fragments)
+#define AB_OWN 64   // own rows of a work-group (4 waves x 16 MFMA columns)
 
 // stage `AB_ROWS` rows [row0, row0 + AB_ROWS) of a [L][ld] operand (channels [0, DH)) as fp32 into lds[row][DH + 4]; rows >= L are zero
 template <typename T, int DH>

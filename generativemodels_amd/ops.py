@@ -2051,21 +2051,43 @@ def _attn_bwd_workspace(d: GmAttnBwdDesc, planner: str, device, may_decline: boo
     return ws
 
 
+def _attention_backward_flash(name: str, q, k, v, o, go, heads: int, scale: float, causal: bool, out=None):
+    """Behind attention_backward and attention_backward_causal (`name`: the caller's, for its error texts, library entry gm_<name> and profile
+    label): head-dim check, gradient buffers, then one descriptor, workspace and launch per group of samples.  Only the causal call groups -- at
+    most 65 535 (sample, head) pairs per launch (grid.y); the unmasked one launches once and leaves the refusal to the library."""
+    require_device(q, k, v, o, go, *(out or ()))
+    dh = q.shape[2] // heads
+    if dh not in ATTENTION_BWD_HEAD_DIMS:
+        raise ValueError(f"{name}: head dim {dh} not in {ATTENTION_BWD_HEAD_DIMS}")
+    b, lq, lk, _ = _attn_bwd_dims(q, k, v, o, go, heads)
+    if causal and lk < lq:
+        raise ValueError("causal attention needs at least as many keys as queries")
+    if causal and heads > 65535:
+        raise ValueError(f"{name}: more than 65535 heads")
+    if out is None:
+        dq, dk, dv = torch.empty_like(q.contiguous()), torch.empty_like(k.contiguous()), torch.empty_like(v.contiguous())
+    else:
+        dq, dk, dv = out
+        for g, t in ((dq, q), (dk, k), (dv, v)):
+            if g.shape != t.shape or g.dtype != t.dtype or (g.shape[0] > 1 and g.stride(0) != g.shape[1] * _kv_ld(g)):
+                raise ValueError(f"{name}: out must be batch-dense (dq, dk, dv) shaped like q, k, v")
+    per = max(1, 65535 // heads)
+    groups = [(s0, min(per, b - s0)) for s0 in range(0, b, per)] if causal else [(0, b)]
+    # (query, key) pairs that carry probability: under the mask Lq * (Lk - Lq) + Lq * (Lq + 1) / 2 of the Lq * Lk
+    pairs = float(lq) * (lk - lq) + 0.5 * lq * (lq + 1) if causal else float(lq) * lk
+    label = f"{name.replace('attention_backward', 'attention_bwd')}<{str(q.dtype).split('.')[-1]}>"
+    for s0, n in groups:
+        d = _attn_bwd_desc(q, k, v, o, go, heads, scale, grads=(dq, dk, dv), sample0=s0, samples=n)
+        ws = _attn_bwd_workspace(d, f"gm_{name}_workspace_bytes", q.device)  # noqa: F841 -- alive until the launch is enqueued
+        _timed(label, dict(flops=14.0 * n * heads * pairs * dh, bytes=float(5 * q.element_size() * q.numel() * n / max(b, 1)), shape=f"B{n} H{heads} L{lq}x{lk} d{dh}"),
+               lambda: check(getattr(lib(), f"gm_{name}")(C.byref(d), _stream()), f"gm_{name}"))
+    return dq, dk, dv
+
+
 def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, go: torch.Tensor, heads: int, scale: float):
     """(dq, dk, dv) of o = softmax(scale q k^T) v per (batch, head) by the fused flash backward (gm_attention_backward): the scores are
     recomputed tile by tile, nothing L x L is stored.  (B, L, heads * dh) operands (channel slices allowed), dh in ATTENTION_BWD_HEAD_DIMS."""
-    require_device(q, k, v, o, go)
-    dh = q.shape[2] // heads
-    if dh not in ATTENTION_BWD_HEAD_DIMS:
-        raise ValueError(f"attention_backward: head dim {dh} not in {ATTENTION_BWD_HEAD_DIMS}")
-    dq, dk, dv = torch.empty_like(q.contiguous()), torch.empty_like(k.contiguous()), torch.empty_like(v.contiguous())
-    d = _attn_bwd_desc(q, k, v, o, go, heads, scale, grads=(dq, dk, dv))
-    b, lq, lk = d.B, d.Lq, d.Lk
-    ws = _attn_bwd_workspace(d, "gm_attention_backward_workspace_bytes", q.device)  # noqa: F841 -- alive until the launch is enqueued
-    _timed(f"attention_bwd<{str(q.dtype).split('.')[-1]}>", dict(flops=14.0 * b * heads * lq * lk * dh, bytes=float(5 * q.element_size() * q.numel()),
-                                                              shape=f"B{b} H{heads} L{lq}x{lk} d{dh}"),
-           lambda: check(lib().gm_attention_backward(C.byref(d), _stream()), "gm_attention_backward"))
-    return dq, dk, dv
+    return _attention_backward_flash("attention_backward", q, k, v, o, go, heads, scale, causal=False)
 
 
 def attention_backward_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, go: torch.Tensor, heads: int, scale: float,
@@ -2074,33 +2096,7 @@ def attention_backward_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     keys j <= i + Lk - Lq) by the causal flash backward (gm_attention_backward_causal): only the tiles that hold a visible pair are recomputed.
     (B, L, heads * dh) operands (channel slices allowed), dh in ATTENTION_BWD_HEAD_DIMS, Lk >= Lq; more than 65 535 (sample, head) pairs go
     through in groups of samples.  out: (dq, dk, dv) to write into -- batch-dense views shaped like q, k, v (any row pitch)."""
-    require_device(q, k, v, o, go, *(out or ()))
-    dh = q.shape[2] // heads
-    if dh not in ATTENTION_BWD_HEAD_DIMS:
-        raise ValueError(f"attention_backward_causal: head dim {dh} not in {ATTENTION_BWD_HEAD_DIMS}")
-    b, lq, lk, _ = _attn_bwd_dims(q, k, v, o, go, heads)
-    if lk < lq:
-        raise ValueError("causal attention needs at least as many keys as queries")
-    if heads > 65535:
-        raise ValueError("attention_backward_causal: more than 65535 heads")
-    if out is None:
-        dq, dk, dv = torch.empty_like(q.contiguous()), torch.empty_like(k.contiguous()), torch.empty_like(v.contiguous())
-    else:
-        dq, dk, dv = out
-        for g, t in ((dq, q), (dk, k), (dv, v)):
-            if g.shape != t.shape or g.dtype != t.dtype or (g.shape[0] > 1 and g.stride(0) != g.shape[1] * _kv_ld(g)):
-                raise ValueError("attention_backward_causal: out must be batch-dense (dq, dk, dv) shaped like q, k, v")
-    per = max(1, 65535 // heads)  # samples per launch: B * H <= 65535 (grid.y)
-    for s0 in range(0, b, per):
-        n = min(per, b - s0)
-        d = _attn_bwd_desc(q, k, v, o, go, heads, scale, grads=(dq, dk, dv), sample0=s0, samples=n)
-        ws = _attn_bwd_workspace(d, "gm_attention_backward_causal_workspace_bytes", q.device)  # noqa: F841 -- alive until the launch is enqueued
-        # visible pairs: Lq * (Lk - Lq) + Lq * (Lq + 1) / 2 of the Lq * Lk
-        pairs = float(lq) * (lk - lq) + 0.5 * lq * (lq + 1)
-        _timed(f"attention_bwd_causal<{str(q.dtype).split('.')[-1]}>",
-               dict(flops=14.0 * n * heads * pairs * dh, bytes=float(5 * q.element_size() * q.numel() * n / max(b, 1)), shape=f"B{n} H{heads} L{lq}x{lk} d{dh}"),
-               lambda: check(lib().gm_attention_backward_causal(C.byref(d), _stream()), "gm_attention_backward_causal"))
-    return dq, dk, dv
+    return _attention_backward_flash("attention_backward_causal", q, k, v, o, go, heads, scale, causal=True, out=out)
 
 
 ATTENTION_BWD_FUSED_HEAD_DIMS = (64, 128, 256)

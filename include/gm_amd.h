@@ -515,7 +515,7 @@ int gm_attention_backward(const GmAttnBwdDesc* d, void* stream);
 /* The same backward under the forward's causal mask (GmAttnDesc.causal: query i sees keys j <= i + Lk - Lq; torch autograd through
  * blocks/selfattention.py:117-147): the same descriptor -- the entry point implies the mask -- and the same preconditions, plus Lk >= Lq.  The
  * log-sum-exp is taken over the visible keys, a masked probability is exactly 0, and every work-group streams only the tiles that hold a
- * visible pair for its rows (generativemodels_amd/csrc/attention_bwd_causal.hip). */
+ * visible pair for its rows (generativemodels_amd/csrc/attention_bwd.hip: the same kernels, compiled with the mask). */
 long long gm_attention_backward_causal_workspace_bytes(const GmAttnBwdDesc* d);
 int gm_attention_backward_causal(const GmAttnBwdDesc* d, void* stream);
 /* The tile walk those kernels run, on the host: the work-group owning queries [64 block, ...) streams the 32-key tiles starting in

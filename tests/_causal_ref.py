@@ -1,5 +1,5 @@
-"""Shared by tests/test_causal_backward_host.py and tests/test_gpu_causal_backward.py: the operands, the fp64 reference and the per-row bar of
-the causal attention backward.  Plain torch on the CPU, no native call."""
+"""Shared by tests/test_causal_backward_host.py, tests/test_gpu_causal_backward.py and tests/test_gpu_flash_backward.py: the operands, the fp64
+reference and the per-row bar of the flash attention backward, with the causal mask (the default) and without.  Plain torch on the CPU, no native call."""
 import math
 
 import torch

@@ -1,4 +1,4 @@
-"""CPU: the host side of the causal attention backward (csrc/attention_bwd_causal.hip) -- the tile walk its kernels run, against a brute-force
+"""CPU: the host side of the causal attention backward (csrc/attention_bwd.hip, CAUSAL) -- the tile walk its kernels run, against a brute-force
 visibility matrix; the "causal" row of the route table; and that the operands of tests/test_gpu_causal_backward.py would expose a mask that is
 off by one key."""
 import ctypes

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the causal flash backward (csrc/attention_bwd_causal.hip: ops.attention_backward_causal, the "causal" route of
+"""GPU (-m gpu): the causal flash backward (csrc/attention_bwd.hip, CAUSAL: ops.attention_backward_causal, the "causal" route of
 autograd.attention_backward_by_route) against fp64 torch autograd of masked-softmax attention, written in _causal_ref.reference, over operands
 already rounded to the tested dtype.  Bars: the flash backward's of tests/test_gpu_backward.py -- 1e-4 (fp32), 1.5e-2 (bf16), times
 max(1, |want|_inf) -- checked per row; every test prints its worst error / bar.  The gradients are written into sentinel-filled buffers with
