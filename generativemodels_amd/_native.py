@@ -203,6 +203,10 @@ PROTOTYPES = {
     "gm_ssim_workspace_bytes": (c_ll, [c_ll, c_ll] + [C.c_int] * 6),
     "gm_ssim_cs": (C.c_int, [c_vp, c_vp, C.c_int, c_ll, c_ll, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int,
                              C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]),
+    "gm_ssim_backward_workspace_bytes": (c_ll, [c_ll, c_ll] + [C.c_int] * 6),
+    "gm_ssim_cs_backward": (C.c_int, [c_vp, c_vp, C.c_int, c_ll, c_ll, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int,
+                                      C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_ll,
+                                      c_vp]),
     "gm_avgpool2_pair": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_mmd_workspace_bytes": (c_ll, [c_ll, c_ll]),
     "gm_mmd": (C.c_int, [c_vp, c_vp, C.c_int, c_ll, c_ll, c_vp, c_vp, c_ll, c_vp]),

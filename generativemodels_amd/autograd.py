@@ -21,6 +21,8 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
   batch_norm_act  forward: per-channel statistics -> gm_bn_finalize (tables + running buffers) -> one apply pass (+ LeakyReLU / ReLU)
                   backward: gm_bn_bwd_stats / _finalize / _apply from the call's own tables (dx, dgamma, dbeta)
   patch_adv_loss  PatchAdversarialLoss over one discriminator output: activation, criterion, reduction and gradient in gm_patch_adv_loss
+  ssim_cs / ms_ssim_factors   (NC[D]HW images, not arenas) the SSIM / cs means and maps, the MS-SSIM factors; backward: gm_ssim_cs_backward per scale,
+                  from the coarsest up, each scale's gradient folded into the next finer scale's store
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -32,7 +34,7 @@ import torch
 
 from . import ops
 
-__all__ = ["cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["ssim_cs", "ms_ssim_factors", "cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -1043,3 +1045,69 @@ def patch_adv_loss(x: torch.Tensor, criterion: str, target: float, activation: b
     element-wise ("none"); differentiable in x."""
     ops.require_device(x)
     return _PatchAdvLoss.apply(x, criterion, float(target), bool(activation), reduction)
+
+
+class _SsimCs(torch.autograd.Function):
+    """ops.ssim_cs (the per-item means and, with want_maps, the maps) as a function of both images.  Only the images are kept: the backward recomputes the
+    moments (ops.ssim_cs_backward) from them and the upstream gradients of whichever outputs were used."""
+
+    @staticmethod
+    def forward(ctx, x, y, taps, c1, c2, want_maps):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, y)
+        ctx.cfg = (taps, c1, c2)
+        ssim_mean, cs_mean, ssim_map, cs_map = ops.ssim_cs(x, y, taps, c1, c2, want_maps=want_maps)
+        return (ssim_mean, cs_mean, ssim_map, cs_map) if want_maps else (ssim_mean, cs_mean)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, y = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        ups = [None if g is None else g.to(torch.float32).contiguous() for g in grads] + [None, None]
+        if all(g is None for g in ups):
+            return (None,) * 6
+        dx, dy = ops.ssim_cs_backward(x, y, *ctx.cfg, g_ssim_mean=ups[0], g_cs_mean=ups[1], g_ssim_map=ups[2], g_cs_map=ups[3], need=need)
+        return dx, dy, None, None, None, None
+
+
+def ssim_cs(x: torch.Tensor, y: torch.Tensor, taps, c1: float, c2: float, want_maps: bool = False):
+    """ops.ssim_cs, differentiable in both images -> (ssim_mean, cs_mean, ssim_map or None, cs_map or None)."""
+    out = _SsimCs.apply(x, y, taps, float(c1), float(c2), bool(want_maps))
+    return out if want_maps else (*out, None, None)
+
+
+class _MsSsimFactors(torch.autograd.Function):
+    """The (scales, batch) fp32 factors of MS-SSIM -- the cs mean of every scale but the last, the ssim mean of the last -- as a function of both images.
+    The forward keeps the pooled fp32 pairs it made anyway; the backward walks from the coarsest scale up and hands each scale's gradient to the next finer
+    scale's gather pass, which folds the pooling's backward into its one store."""
+
+    @staticmethod
+    def forward(ctx, x, y, taps, c1, c2, scales):
+        ctx.cfg = (taps, c1, c2)
+        pairs, factors = [(x, y)], []
+        for scale in range(scales):
+            ssim_mean, cs_mean, _, _ = ops.ssim_cs(*pairs[-1], taps, c1, c2)
+            factors.append(ssim_mean if scale == scales - 1 else cs_mean)
+            if scale != scales - 1:
+                pairs.append(ops.avgpool2_pair(*pairs[-1]))
+        ctx.save_for_backward(*(t for pair in pairs for t in pair))
+        return torch.stack(factors)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        g = g.to(torch.float32).contiguous()
+        last = len(saved) // 2 - 1
+        pooled = None
+        for scale in range(last, -1, -1):
+            up = dict(g_ssim_mean=g[scale]) if scale == last else dict(g_cs_mean=g[scale])
+            pooled = ops.ssim_cs_backward(saved[2 * scale], saved[2 * scale + 1], *ctx.cfg, pooled_grad=pooled, need=need, **up)
+        return pooled[0], pooled[1], None, None, None, None
+
+
+def ms_ssim_factors(x: torch.Tensor, y: torch.Tensor, taps, c1: float, c2: float, scales: int) -> torch.Tensor:
+    """(scales, batch) fp32: relu and the product of powers over them stay torch arithmetic, which torch differentiates."""
+    return _MsSsimFactors.apply(x, y, taps, float(c1), float(c2), int(scales))

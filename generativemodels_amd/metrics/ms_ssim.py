@@ -6,14 +6,14 @@ from collections.abc import Sequence
 
 import torch
 
-from .. import ops
+from .. import autograd, ops
 from ._base import CumulativeRegressionMetric, MetricReduction
-from .ssim import KernelType, _check_dims, _constants, _per_axis, window_taps
+from .ssim import KernelType, _check_dims, _constants, _per_axis, _wants_grad, window_taps
 
 
 class MultiScaleSSIMMetric(CumulativeRegressionMetric):
     """prod_j relu(cs_j) ** w_j over the scales j, the last factor being relu(ssim) of the coarsest scale; each scale halves every extent
-    (2x average pooling, floor).  One value per batch item.
+    (2x average pooling, floor).  One value per batch item, differentiable in both images.
 
     Args: as SSIMMetric, plus
         weights: one exponent per scale.
@@ -45,14 +45,18 @@ class MultiScaleSSIMMetric(CumulativeRegressionMetric):
                                  f"larger than {(k - 1) * divisor}.")
         taps = window_taps(self.spatial_dims, self.kernel_type, self.kernel_size, self.kernel_sigma)
         c1, c2 = _constants(self.data_range, self.k1, self.k2)
-        factors = []
-        last = len(self.weights) - 1
-        for scale in range(len(self.weights)):
-            ssim_mean, cs_mean, _, _ = ops.ssim_cs(y_pred, y, taps, c1, c2)
-            factors.append(ssim_mean if scale == last else cs_mean)
-            if scale != last:
-                y_pred, y = ops.avgpool2_pair(y_pred, y)
+        if _wants_grad(y_pred, y):
+            stacked = autograd.ms_ssim_factors(y_pred, y, taps, c1, c2, len(self.weights))
+        else:
+            factors = []
+            last = len(self.weights) - 1
+            for scale in range(len(self.weights)):
+                ssim_mean, cs_mean, _, _ = ops.ssim_cs(y_pred, y, taps, c1, c2)
+                factors.append(ssim_mean if scale == last else cs_mean)
+                if scale != last:
+                    y_pred, y = ops.avgpool2_pair(y_pred, y)
+            stacked = torch.stack(factors)
         # (scales, batch) numbers: combined in fp64 on the device, rounded once
-        stacked = torch.relu(torch.stack(factors).double())
+        stacked = torch.relu(stacked.double())
         weights = torch.tensor(self.weights, dtype=torch.float32, device=stacked.device).double().view(-1, 1)
         return torch.prod(stacked ** weights, dim=0).float().view(-1, 1)

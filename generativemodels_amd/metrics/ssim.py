@@ -8,7 +8,7 @@ from enum import Enum
 
 import torch
 
-from .. import ops
+from .. import autograd, ops
 from ._base import CumulativeRegressionMetric, MetricReduction
 
 
@@ -60,21 +60,26 @@ def _constants(data_range: float, k1: float, k2: float) -> tuple[float, float]:
     return (k1 * data_range) ** 2, (k2 * data_range) ** 2
 
 
+def _wants_grad(y_pred: torch.Tensor, y: torch.Tensor) -> bool:
+    """The differentiable route (autograd.ssim_cs / ms_ssim_factors: the same forward launches, plus a graph node) is taken only where a gradient can flow."""
+    return torch.is_grad_enabled() and (y_pred.requires_grad or y.requires_grad)
+
+
 def compute_ssim_and_cs(y_pred: torch.Tensor, y: torch.Tensor, spatial_dims: int, data_range: float = 1.0,
                         kernel_type: KernelType | str = KernelType.GAUSSIAN, kernel_size: int | Sequence[int] = 11,
                         kernel_sigma: float | Sequence[float] = 1.5, k1: float = 0.01, k2: float = 0.03) -> tuple[torch.Tensor, torch.Tensor]:
-    """-> (ssim, cs): fp32 maps of shape (batch, channel, *(n - k + 1)) over the positions where the window fits."""
+    """-> (ssim, cs): fp32 maps of shape (batch, channel, *(n - k + 1)) over the positions where the window fits; differentiable in both images."""
     if y.shape != y_pred.shape:
         raise ValueError(f"y_pred and y should have same shapes, got {y_pred.shape} and {y.shape}.")
     taps = window_taps(spatial_dims, kernel_type, kernel_size, kernel_sigma)
     c1, c2 = _constants(data_range, k1, k2)
-    _, _, ssim_map, cs_map = ops.ssim_cs(y_pred, y, taps, c1, c2, want_maps=True)
+    _, _, ssim_map, cs_map = (autograd if _wants_grad(y_pred, y) else ops).ssim_cs(y_pred, y, taps, c1, c2, want_maps=True)
     return ssim_map, cs_map
 
 
 class SSIMMetric(CumulativeRegressionMetric):
     """SSIM(x, y) = (2 mu_x mu_y + c1)(2 sigma_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(sigma_x^2 + sigma_y^2 + c2)), averaged over channels and
-    window positions: one value per batch item.
+    window positions: one value per batch item, differentiable in both images (`(1 - metric(recon, images).mean()).backward()`).
 
     Args:
         spatial_dims: 2 or 3.
@@ -104,5 +109,5 @@ class SSIMMetric(CumulativeRegressionMetric):
             raise ValueError(f"y_pred and y should have same shapes, got {y_pred.shape} and {y.shape}.")
         taps = window_taps(self.spatial_dims, self.kernel_type, self.kernel_size, self.kernel_sigma)
         c1, c2 = _constants(self.data_range, self.k1, self.k2)
-        ssim_mean, _, _, _ = ops.ssim_cs(y_pred, y, taps, c1, c2)
+        ssim_mean, _, _, _ = (autograd if _wants_grad(y_pred, y) else ops).ssim_cs(y_pred, y, taps, c1, c2)
         return ssim_mean.view(-1, 1)

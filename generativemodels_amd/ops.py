@@ -2672,7 +2672,7 @@ def vq_gather(indices: torch.Tensor, embedding: torch.Tensor, dtype: torch.dtype
     return (out, err) if x is not None else out
 
 
-# ---- generative.metrics (csrc/metrics.hip) ---------------------------------------------------------------------------------------------
+# ---- generative.metrics (csrc/metrics.hip, csrc/metrics_bwd.hip) ------------------------------------------------------------------------
 _METRIC_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # the metric kernels upcast in registers and also read fp16
 
 
@@ -2697,17 +2697,15 @@ def _volumes(t: torch.Tensor):
     raise ValueError(f"expected a (B, C, H, W) or (B, C, D, H, W) tensor, got {t.dim()} dimensions")
 
 
-def ssim_cs(x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]], c1: float, c2: float, want_maps: bool = False):
-    """SSIM and contrast sensitivity of two NC[D]HW images under a separable window: `taps` holds one normalised 1-D table per spatial axis.
-    -> (ssim_mean (B,), cs_mean (B,), ssim_map, cs_map): fp32 means over channels and "valid" positions, and the fp32 maps
-    (B, C, *valid extents) or None."""
+def _ssim_operands(who: str, x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]]):
+    """The argument checks the SSIM forward and backward share -> ((B, C, D, H, W), (kd, kh, kw), the three C tap tables, valid spatial extents)."""
     require_device(x, y)
     if x.shape != y.shape or x.dtype != y.dtype:
-        raise ValueError(f"ssim_cs operands must share shape and dtype, got {tuple(x.shape)} {x.dtype} and {tuple(y.shape)} {y.dtype}")
+        raise ValueError(f"{who} operands must share shape and dtype, got {tuple(x.shape)} {x.dtype} and {tuple(y.shape)} {y.dtype}")
     B, Cn, D, H, W = _volumes(x)
     nsp = x.dim() - 2
     if len(taps) != nsp:
-        raise ValueError(f"ssim_cs needs one tap table per spatial axis ({nsp}), got {len(taps)}")
+        raise ValueError(f"{who} needs one tap table per spatial axis ({nsp}), got {len(taps)}")
     tabs = ([[1.0]] if nsp == 2 else []) + [[float(v) for v in t] for t in taps]
     kd, kh, kw = (len(t) for t in tabs)
     limit = ssim_max_window()
@@ -2716,16 +2714,23 @@ def ssim_cs(x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]], c
     if kd > D or kh > H or kw > W:
         raise ValueError(f"SSIM window {tuple(len(t) for t in taps)} is larger than the image {tuple(x.shape[2:])}")
     if B * Cn == 0 or B * Cn > 65535:
-        raise ValueError(f"ssim_cs takes 1..65535 (batch x channel) volumes, got {B * Cn}")
+        raise ValueError(f"{who} takes 1..65535 (batch x channel) volumes, got {B * Cn}")
+    ctabs = [(C.c_float * len(t))(*t) for t in tabs]
+    return (B, Cn, D, H, W), (kd, kh, kw), ctabs, (D - kd + 1, H - kh + 1, W - kw + 1)[3 - nsp:]
+
+
+def ssim_cs(x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]], c1: float, c2: float, want_maps: bool = False):
+    """SSIM and contrast sensitivity of two NC[D]HW images under a separable window: `taps` holds one normalised 1-D table per spatial axis.
+    -> (ssim_mean (B,), cs_mean (B,), ssim_map, cs_map): fp32 means over channels and "valid" positions, and the fp32 maps
+    (B, C, *valid extents) or None."""
+    (B, Cn, D, H, W), (kd, kh, kw), ctabs, out_sp = _ssim_operands("ssim_cs", x, y, taps)
     x, y = x.contiguous(), y.contiguous()
     ws_bytes = int(lib().gm_ssim_workspace_bytes(B, Cn, D, H, W, kd, kh, kw))
     if ws_bytes < 0:
         raise ValueError("ssim_cs: geometry refused by the planner")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     means = torch.empty((2, B), dtype=torch.float32, device=x.device)
-    out_sp = (D - kd + 1, H - kh + 1, W - kw + 1)[3 - nsp:]
     maps = torch.empty((2, B, Cn, *out_sp), dtype=torch.float32, device=x.device) if want_maps else None
-    ctabs = [(C.c_float * len(t))(*t) for t in tabs]
     nout = float(B * Cn * math.prod(out_sp))
     _timed("ssim_cs", dict(flops=nout * (10.0 * (kd + kh + kw) + 20.0), bytes=float(2 * x.element_size() * x.numel() + (8.0 * nout if want_maps else 0.0)),
                            shape=str(tuple(x.shape))),
@@ -2733,6 +2738,50 @@ def ssim_cs(x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]], c
                                           float(c1), float(c2), means[0].data_ptr(), means[1].data_ptr(), _ptr(None if maps is None else maps[0]),
                                           _ptr(None if maps is None else maps[1]), ws.data_ptr(), ws_bytes, _stream()), "gm_ssim_cs"))
     return means[0], means[1], (None if maps is None else maps[0]), (None if maps is None else maps[1])
+
+
+def ssim_cs_backward(x: torch.Tensor, y: torch.Tensor, taps: Sequence[Sequence[float]], c1: float, c2: float, g_ssim_mean: Optional[torch.Tensor] = None,
+                     g_cs_mean: Optional[torch.Tensor] = None, g_ssim_map: Optional[torch.Tensor] = None, g_cs_map: Optional[torch.Tensor] = None,
+                     pooled_grad: Optional[tuple] = None, need: tuple = (True, True)):
+    """The gradient of ssim_cs's outputs with respect to both images -> (dx, dy) in the images' dtype, None where `need` is False.
+    Upstream: g_*_mean (B,) for the per-item means and / or g_*_map (B, C, *valid extents) for the maps, fp32, at least one.  pooled_grad: the fp32
+    gradients (dx, dy) with respect to avgpool2_pair(x, y), folded in before the one store (either entry may be None)."""
+    (B, Cn, D, H, W), (kd, kh, kw), ctabs, out_sp = _ssim_operands("ssim_cs_backward", x, y, taps)
+    ups = dict(g_ssim_mean=g_ssim_mean, g_cs_mean=g_cs_mean, g_ssim_map=g_ssim_map, g_cs_map=g_cs_map)
+    if all(g is None for g in ups.values()):
+        raise ValueError("ssim_cs_backward needs at least one upstream gradient")
+    if not (need[0] or need[1]):
+        raise ValueError("ssim_cs_backward: no gradient requested")
+    require_device(*ups.values())
+    for name, g in ups.items():
+        want = (B,) if name.endswith("mean") else (B, Cn, *out_sp)
+        if g is not None and (tuple(g.shape) != want or g.dtype != torch.float32):
+            raise ValueError(f"ssim_cs_backward: {name} must be float32 of shape {want}, got {g.dtype} {tuple(g.shape)}")
+    three_d = x.dim() == 5
+    pooled = (None, None) if pooled_grad is None else tuple(pooled_grad)
+    pool_sp = ((D // 2,) if three_d else ()) + (H // 2, W // 2)
+    require_device(*pooled)
+    for g in pooled:
+        if g is not None and (min(pool_sp) < 1 or tuple(g.shape) != (B, Cn, *pool_sp) or g.dtype != torch.float32):
+            raise ValueError(f"ssim_cs_backward: a pooled gradient must be float32 of shape {(B, Cn, *pool_sp)}, got {g.dtype} {tuple(g.shape)}")
+    x, y = x.contiguous(), y.contiguous()
+    ups = {k: None if g is None else g.contiguous() for k, g in ups.items()}
+    pooled = tuple(None if g is None else g.contiguous() for g in pooled)
+    ws_bytes = int(lib().gm_ssim_backward_workspace_bytes(B, Cn, D, H, W, kd, kh, kw))
+    if ws_bytes < 0:
+        raise ValueError("ssim_cs_backward: geometry refused by the planner")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    dx = torch.empty_like(x) if need[0] else None
+    dy = torch.empty_like(y) if need[1] else None
+    nout, nin = float(B * Cn * math.prod(out_sp)), float(x.numel())
+    _timed("ssim_cs_backward", dict(flops=nout * (10.0 * (kd + kh + kw) + 40.0) + nin * (8.0 * (kd + kh + kw) + 8.0),
+                                    bytes=float(4 * x.element_size() * x.numel() + 32.0 * nout + x.element_size() * nin * (bool(need[0]) + bool(need[1]))),
+                                    shape=str(tuple(x.shape))),
+           lambda: check(lib().gm_ssim_cs_backward(x.data_ptr(), y.data_ptr(), metric_dt_code(x.dtype), B, Cn, D, H, W, ctabs[0], kd, ctabs[1], kh, ctabs[2], kw,
+                                                   float(c1), float(c2), _ptr(ups["g_ssim_mean"]), _ptr(ups["g_cs_mean"]), _ptr(ups["g_ssim_map"]),
+                                                   _ptr(ups["g_cs_map"]), _ptr(pooled[0]), _ptr(pooled[1]), int(three_d), _ptr(dx), _ptr(dy), ws.data_ptr(),
+                                                   ws_bytes, _stream()), "gm_ssim_cs_backward"))
+    return dx, dy
 
 
 def avgpool2_pair(a: torch.Tensor, b: torch.Tensor):

@@ -581,6 +581,18 @@ long long gm_ssim_workspace_bytes(long long B, long long C, int D, int H, int W,
 int gm_ssim_cs(const void* x, const void* y, int dtype, long long B, long long C, int D, int H, int W, const float* taps_d, int kd,
                const float* taps_h, int kh, const float* taps_w, int kw, float c1, float c2, float* ssim_mean, float* cs_mean,
                float* ssim_map, float* cs_map, void* workspace, long long workspace_bytes, void* stream);
+/* The backward of gm_ssim_cs with respect to both images, in two launches: the moments are recomputed and d(loss) / d(moment) is stored per valid position
+ * (four fp32 maps: the workspace, gm_ssim_backward_workspace_bytes(...) bytes, no initialisation), then filtered with the transposed separable correlation
+ * over the input extents and combined with x and y.  Upstream of position p of batch item b: g_ssim_mean[b] / count + g_ssim_map[p] for ssim and the same
+ * for cs, count = C * Do * Ho * Wo; each of the four operands may be NULL (not all).  dx, dy: (B, C, D, H, W) in the dtype of x, either may be NULL.
+ * pooled_dx / pooled_dy (fp32 (B, C, D / 2, H / 2, W / 2), D as it is with pool_depth = 0; NULL: none): the gradient with respect to gm_avgpool2_pair's
+ * outputs of these images -- its element [q / 2] / 2^d is added to dx / dy at q before the one store, nothing at an odd tail the floor pooling dropped.
+ * No atomics: bit-reproducible, a batch item's gradient does not depend on its neighbours, and dx alone has the bits it has next to dy. */
+long long gm_ssim_backward_workspace_bytes(long long B, long long C, int D, int H, int W, int kd, int kh, int kw);
+int gm_ssim_cs_backward(const void* x, const void* y, int dtype, long long B, long long C, int D, int H, int W, const float* taps_d, int kd,
+                        const float* taps_h, int kh, const float* taps_w, int kw, float c1, float c2, const float* g_ssim_mean,
+                        const float* g_cs_mean, const float* g_ssim_map, const float* g_cs_map, const float* pooled_dx, const float* pooled_dy,
+                        int pool_depth, void* dx, void* dy, void* workspace, long long workspace_bytes, void* stream);
 /* avg_pool{2,3}d(kernel_size=2) of both images between two MS-SSIM scales (metrics/ms_ssim.py:140-141): (nvol, D, H, W) -> fp32 (nvol, D / 2, H / 2, W / 2),
  * floor on odd extents; pool_depth = 0 leaves D as it is (2-D). */
 int gm_avgpool2_pair(const void* a, const void* b, int dtype, float* out_a, float* out_b, long long nvol, int D, int H, int W, int pool_depth,

@@ -2,6 +2,7 @@
 
     python tools/bench_metrics.py                 # every configuration and implementation, one child process each
     python tools/bench_metrics.py --config ssim3d_128 --impl native
+    python tools/bench_metrics.py --backward      # forward + backward: the native kernels against torch autograd through the dense sequence
 
 Each (configuration, implementation) step is its own process under `timeout -k 10`; the steps are chained -- the first one that fails ends the
 run.  A step warms its shapes up, then times `reps` repetitions with device events and prints ONE JSON line: median / min / max milliseconds
@@ -79,7 +80,7 @@ def native_call(cfg, x, y):
     return lambda: metric._compute_metric(x, y)
 
 
-def run_step(name, impl, reps, warmup):
+def run_step(name, impl, reps, warmup, backward=False):
     import torch
 
     assert torch.cuda.is_available(), "bench_metrics needs an MI355X"
@@ -88,6 +89,15 @@ def run_step(name, impl, reps, warmup):
     y = torch.rand(cfg["shape"], generator=g).to("cuda:0")
     x = (y + 0.1 * torch.rand(cfg["shape"], generator=g).to("cuda:0")).clamp(0, 1)
     call = (native_call if impl == "native" else torch_call)(cfg, x, y)
+    if backward:  # one training-style step: the value, then d(sum of the values) / d(both images)
+        x.requires_grad_(True), y.requires_grad_(True)
+        forward = call
+
+        def call():
+            x.grad = y.grad = None
+            value = forward()
+            value.sum().backward()
+            return value.detach()
     for _ in range(warmup):
         value = call()
     torch.cuda.synchronize()
@@ -101,9 +111,11 @@ def run_step(name, impl, reps, warmup):
         times.append(e0.elapsed_time(e1))
     med = statistics.median(times)
     one_pass = 2 * x.numel() * x.element_size()  # both images once; MS-SSIM's pooled scales add 1/7 (3-D) of that again, not counted
-    rec = dict(config=name, impl=impl, shape=list(cfg["shape"]), kernel_size=cfg["kernel_size"], reps=reps, ms_median=med, ms_min=min(times), ms_max=max(times),
+    rec = dict(config=name, impl=impl, backward=backward, shape=list(cfg["shape"]), kernel_size=cfg["kernel_size"], reps=reps, ms_median=med, ms_min=min(times), ms_max=max(times),
                value=[float(v) for v in value.flatten().tolist()], one_pass_bytes=one_pass, one_pass_gb_per_s=one_pass / (med * 1e-3) / 1e9,
                share_of_hbm_peak=one_pass / (med * 1e-3) / HBM_PEAK, peak_mem_mb=torch.cuda.max_memory_allocated() / 2 ** 20)
+    if backward:
+        rec.update(grad_abs_max=[float(x.grad.abs().max()), float(y.grad.abs().max())])
     if impl == "native":  # per-launch split of one more call (device events around each launch)
         from generativemodels_amd import ops
 
@@ -120,16 +132,17 @@ def main():
     ap.add_argument("--impl", choices=["native", "torch"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--backward", action="store_true", help="time forward + backward with both images requiring a gradient")
     a = ap.parse_args()
     if a.config and a.impl:
-        run_step(a.config, a.impl, a.reps, a.warmup)
+        run_step(a.config, a.impl, a.reps, a.warmup, a.backward)
         return 0
     # the native steps first, then the dense sequence from the cheapest configuration to the dearest: a dense step that fails ends the run late
     names = [a.config] if a.config else list(CONFIGS)
     steps = [(n, i) for i in ([a.impl] if a.impl else ["native", "torch"]) for n in (names if i == "native" else names[::-1])]
     for name, impl in steps:
         cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT[impl]), sys.executable, os.path.abspath(__file__), "--config", name, "--impl", impl,
-               "--reps", str(a.reps if impl == "native" else max(5, a.reps // 3)), "--warmup", str(a.warmup if impl == "native" else 2)]
+               "--reps", str(a.reps if impl == "native" else max(5, a.reps // 3)), "--warmup", str(a.warmup if impl == "native" else 2)] + (["--backward"] if a.backward else [])
         rc = subprocess.run(cmd, cwd=ROOT).returncode
         if rc != 0:  # chained: nothing more is started on the device after a step that failed
             print(json.dumps(dict(config=name, impl=impl, failed=True, returncode=rc)), flush=True)
