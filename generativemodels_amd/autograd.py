@@ -3,12 +3,17 @@ reference: tutorials/generative/distributed_training/ddpm_training_ddp.py:249-27
 backward pass is torch autograd over nn.Conv3d / nn.GroupNorm / nn.SiLU).
 
 Every function here works on arena tensors (N, *spatial, C) and runs native kernels in both directions:
-  conv            forward: the fused convolution (bias, per-sample row vector, residual in the epilogue)
-                  dx: the transposed convolution of gy with the same weight (the forward LDS-DMA kernel at stride 1)
-                  dW: gm_conv_wgrad (MFMA, split-K, deterministic); db / d(row vector): column sums of gy
+  conv            ONE autograd function (_Conv) behind conv / linear / conv_transpose / conv_dilated / conv_transpose_dilated / upsample_conv: each
+                  wrapper only writes the layer's geometry into a ConvSpec
+                  forward: the fused convolution (bias, per-sample row vector, residual, activation in the epilogue)
+                  dx: the adjoint convolution of gy with the same weight (_data_grad) -- the transposed convolution (the forward LDS-DMA kernel at
+                  stride 1, the sub-pixel kernel at k3 s2 in 3-D), the plain convolution for a transposed layer
+                  dW: ops.conv_wgrad, (x, gy) exchanged for a transposed layer; its route by ops.conv_wgrad_route -- gm_conv_wgrad (MFMA, split-K,
+                  deterministic), over phase images at k4 s2, over zero-padded channels, or per tap (the dilated wrappers, at any dilation)
+                  db / d(row vector): column sums of gy
+                  upsample_conv: nearest 2x folded into the convolution; backward: dgrad on the fine grid, 2x sum-pool; dW against the upsampled input
   group_norm_act  forward: per-channel statistics -> (scale, shift) -> one apply pass (+ SiLU)
                   backward: gm_gn_bwd_stats / _finalize / _apply (dx, dgamma, dbeta)
-  upsample_conv   nearest 2x folded into the convolution; backward: dgrad on the fine grid, 2x sum-pool; dW against the upsampled input
   attention       forward: the flash-attention kernel (head dims up to 256; 257 .. 1024 on the sliced wide-head kernel); backward: one of four
                   routes, chosen from dtype, (sample, head) pairs, tokens and head dim by the table of attention_backward_route -- the fused
                   bf16 LDS-DMA flash backward, the bf16-MFMA score pass + weight-gradient kernels, the fused fp32 flash backward (head dims
@@ -28,6 +33,7 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
 There is no eager fallback: a CPU tensor raises in the first native call."""
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -41,66 +47,99 @@ def _tup(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (int(v),) * n
 
 
-def _weight_grad(weight: torch.Tensor, shape, run):
+def _weight_grad(weight: torch.Tensor, shape, run, direct: bool = True):
     """The weight gradient of one layer: `run(out, accumulate)` launches gm_conv_wgrad (fp32 [Cout, Cin, *k] result).  When the parameter's
     `.grad` is a GradientReducer bucket view (fp32 master parameters: parallel.direct_grad_hook), the kernel's final reduction ADDS INTO IT
     and autograd gets None (no `add_` launch for this parameter; the reducer learns of the gradient from the engine's post-accumulate hook, which
-    fires once after every use of the weight); otherwise the fresh tensor goes back to autograd in the parameter's dtype."""
+    fires once after every use of the weight); otherwise -- and always with direct=False -- the fresh tensor goes back to autograd in the
+    parameter's dtype."""
     from .parallel import direct_grad_hook
 
-    if direct_grad_hook(weight):
+    if direct and direct_grad_hook(weight):
         run(weight.grad.view(shape), True)  # readiness is signalled by the engine's post-accumulate hook, after ALL uses of the weight
         return None
     return run(None, False).reshape(weight.shape).to(weight.dtype)
 
 
+ConvSpec = namedtuple("ConvSpec", "kernel stride padding pad_hi dilation transposed output_padding upsample by_taps post_act want_stats allow_subpixel",
+                      defaults=(1, 0, None, 1, False, 0, False, False, "none", False, True))
+
+
+def adjoint_output_padding(in_sp, out_sp, k, s, p, phi, d):
+    """The output_padding with which the transposed convolution of a convolution's output gradient (extents `out_sp`) has the input's extents `in_sp`;
+    per-axis tuples, `p` / `phi` the low / high pads.  ValueError where there is none in [0, stride): `out_sp` is no output of this convolution over `in_sp`."""
+    opad = tuple(in_sp[i] - ((out_sp[i] - 1) * s[i] - p[i] - phi[i] + d[i] * (k[i] - 1) + 1) for i in range(len(in_sp)))
+    if any(o < 0 or o >= s[i] for i, o in enumerate(opad)):
+        raise ValueError(f"convolution geometry is not invertible: output_padding {opad}")
+    return opad
+
+
+def _data_grad(spec, x_shape, gy, weight):
+    """dx of every convolution: the adjoint convolution of gy with the same weight."""
+    nsp = len(x_shape) - 2
+    if spec.upsample:  # the transposed convolution on the fine grid, then the sum over each 2^d cell
+        du = ops.conv(gy, weight, None, kernel=spec.kernel, stride=spec.stride, padding=spec.padding, transposed=True)
+        return ops.scale(ops.resample2x(du, "down"), float(2 ** nsp))
+    if spec.transposed:  # [Cin, Cout, *k] read as a Conv weight
+        dx = ops.conv(gy, weight, None, kernel=spec.kernel, stride=spec.stride, padding=spec.padding, dilation=spec.dilation)
+        if dx.shape != x_shape:
+            raise ValueError(f"transposed-convolution geometry is not invertible: {tuple(dx.shape)} vs {tuple(x_shape)}")
+        return dx
+    k, s, p, d = (_tup(v, nsp) for v in (spec.kernel, spec.stride, spec.padding, spec.dilation))
+    phi = _tup(spec.pad_hi, nsp) if spec.pad_hi is not None else p
+    opad = adjoint_output_padding(x_shape[1:-1], gy.shape[1:-1], k, s, p, phi, d)
+    dx = None
+    if nsp == 3 and k == (3, 3, 3) and s == (2, 2, 2) and p[0] == p[1] == p[2] and phi == (1, 1, 1) and not spec.by_taps:
+        # stride 2 (the Downsample convolutions): one sub-pixel launch on gy instead of a convolution over its zero-inserted image
+        dx = ops.conv_stride2_dgrad(gy, weight, x_shape[1:4], p[0])
+    if dx is None:
+        dx = ops.conv(gy, weight, None, kernel=k, stride=s, padding=p, pad_hi=phi, dilation=d, transposed=True, output_padding=opad)
+    return dx
+
+
 class _Conv(torch.autograd.Function):
+    """Every convolution layer: y = post_act(conv(x, weight) + bias + rowvec[n] + res) in the geometry of `spec` (a ConvSpec)."""
+
     @staticmethod
-    def forward(ctx, x, weight, bias, rowvec, res, kernel, stride, padding, pad_hi, post_act="none"):
+    def forward(ctx, x, weight, bias, rowvec, res, spec):
         # want_stats: the fast kernels leave the per-channel statistics of y on the tensor, so the GroupNorm that follows needs no pass
-        y = ops.conv(x, weight, bias, kernel=kernel, stride=stride, padding=padding, pad_hi=pad_hi, rowvec=rowvec, res=res,
-                     want_stats=x.dim() >= 4 and post_act == "none", post_act=post_act)
-        ctx.post_act = post_act
-        if post_act != "none":  # the epilogue activation is differentiated from its OUTPUT (ReLU: y > 0 <=> z > 0): y is all the backward needs
-            ctx.save_for_backward(x, weight, y)
-        else:
-            ctx.save_for_backward(x, weight)
-        ctx.geom = (kernel, stride, padding, pad_hi)
+        y = ops.conv(x, weight, bias, kernel=spec.kernel, stride=spec.stride, padding=spec.padding, pad_hi=spec.pad_hi, dilation=spec.dilation,
+                     transposed=spec.transposed, output_padding=spec.output_padding, upsample=spec.upsample, rowvec=rowvec, res=res,
+                     post_act=spec.post_act, want_stats=spec.want_stats, allow_subpixel=spec.allow_subpixel)
+        # the epilogue activation is differentiated from its OUTPUT (ReLU: y > 0 <=> z > 0): y is all the backward needs
+        ctx.save_for_backward(x, weight, *(() if spec.post_act == "none" else (y,)))
+        ctx.spec = spec
         ctx.bias_dtype = None if bias is None else bias.dtype
         ctx.row_shape = None if rowvec is None else tuple(rowvec.shape)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        saved = ctx.saved_tensors  # (read ONCE: under torch.utils.checkpoint every access re-triggers the unpack hooks)
-        x, weight = saved[:2]
-        kernel, stride, padding, pad_hi = ctx.geom
+        x, weight, *y = ctx.saved_tensors  # (read ONCE: under torch.utils.checkpoint every access re-triggers the unpack hooks)
+        spec = ctx.spec
         gy = gy.contiguous()
-        if ctx.post_act != "none":
-            gy = ops.act_backward(saved[2], gy, ctx.post_act)
-        nsp = x.dim() - 2
-        k, s, p = _tup(kernel, nsp), _tup(stride, nsp), _tup(padding, nsp)
-        phi = _tup(pad_hi, nsp) if pad_hi is not None else p
+        if y:
+            gy = ops.act_backward(y[0], gy, spec.post_act)
         dx = dw = db = drow = dres = None
         if ctx.needs_input_grad[0]:
-            opad = tuple(x.shape[1 + i] - ((gy.shape[1 + i] - 1) * s[i] - p[i] - phi[i] + k[i]) for i in range(nsp))
-            if any(o < 0 or o >= s[i] for i, o in enumerate(opad)):
-                raise ValueError(f"convolution geometry is not invertible: output_padding {opad}")
-            dx = None
-            if nsp == 3 and k == (3, 3, 3) and s == (2, 2, 2) and p[0] == p[1] == p[2] and phi == (1, 1, 1):
-                # stride 2 (the Downsample convolutions): one sub-pixel launch on gy instead of a convolution over its zero-inserted image
-                dx = ops.conv_stride2_dgrad(gy, weight, x.shape[1:4], p[0])
-            if dx is None:
-                dx = ops.conv(gy, weight, None, kernel=k, stride=s, padding=p, pad_hi=phi, transposed=True, output_padding=opad)
+            dx = _data_grad(spec, x.shape, gy, weight)
         if ctx.needs_input_grad[1]:
-            dw = _weight_grad(weight, (weight.shape[0], weight.shape[1], *k), lambda out, acc: ops.conv_wgrad(x, gy, k, s, p, out=out, accumulate=acc))
+            # a transposed convolution is the adjoint of the convolution with the same weight read as [out = Cin, in = Cout]: its weight gradient is
+            # that convolution's with the roles of input and output gradient exchanged
+            a, b = (gy, x) if spec.transposed else (ops.resample2x(x, "up") if spec.upsample else x, gy)
+            k = _tup(spec.kernel, x.dim() - 2)
+
+            def run(out, acc):
+                return ops.conv_wgrad(a, b, k, spec.stride, spec.padding, out=out, accumulate=acc, dilation=spec.dilation, by_taps=spec.by_taps)
+            # (the per-tap layers hand a fresh tensor back to autograd: the direct-to-bucket path is not theirs)
+            dw = _weight_grad(weight, (weight.shape[0], weight.shape[1], *k), run, direct=not spec.by_taps)
         if ctx.needs_input_grad[2]:
             db = ops.bias_grad(gy).to(ctx.bias_dtype)
         if ctx.needs_input_grad[3]:
             drow = ops.bias_grad(gy, per_sample=True) if ctx.row_shape[0] != 1 else ops.bias_grad(gy)[None]
         if ctx.needs_input_grad[4]:
             dres = gy
-        return dx, dw, db, drow, dres, None, None, None, None, None
+        return dx, dw, db, drow, dres, None
 
 
 def conv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, kernel, stride=1, padding=0, pad_hi=None,
@@ -108,172 +147,39 @@ def conv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = N
     """y = post_act(conv(x, weight) + bias + rowvec[n] + res) over an arena tensor; differentiable in x, weight, bias, rowvec (fp32 [N or 1,
     Cout]) and res.  post_act: "none" or "relu" (fused into the epilogue; the VQ-VAE's convolution + ReLU layers).  Kernel 1 or 3 at stride 1 / 2,
     and kernel 4 at stride 2 (the VQ-VAE down-sampling convolutions: weight gradient over the phase images of x, ops.conv_wgrad)."""
-    return _Conv.apply(x, weight, bias, rowvec, res, kernel, stride, padding, pad_hi, post_act)
+    return _Conv.apply(x, weight, bias, rowvec, res, ConvSpec(kernel, stride, padding, pad_hi, post_act=post_act,
+                                                              want_stats=x.dim() >= 4 and post_act == "none"))
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nn.Linear over the last dim of (N, L, C)."""
     if x.dim() != 3:
         raise ValueError("linear expects (N, L, C)")
-    return _Conv.apply(x, weight, bias, None, res, 1, 1, 0, None)
-
-
-class _ConvTranspose(torch.autograd.Function):
-    """nn.ConvTranspose{2,3}d (weight [Cin, Cout, *k]): AutoencoderKL's `use_convtranspose` up-sampling (autoencoderkl.py:54-63: k3 s2 p1 op1).
-    It is the adjoint of the convolution with the same weight read as [out = Cin, in = Cout]: dx is that convolution applied to gy, and
-    dW the weight gradient of that convolution with the roles of input and output gradient exchanged."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, kernel, stride, padding, output_padding, post_act="none"):
-        y = ops.conv(x, weight, bias, kernel=kernel, stride=stride, padding=padding, transposed=True, output_padding=output_padding,
-                     want_stats=post_act == "none", post_act=post_act)
-        ctx.post_act = post_act
-        if post_act != "none":
-            ctx.save_for_backward(x, weight, y)
-        else:
-            ctx.save_for_backward(x, weight)
-        ctx.geom = (kernel, stride, padding)
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        saved = ctx.saved_tensors  # (read ONCE: under torch.utils.checkpoint every access re-triggers the unpack hooks)
-        x, weight = saved[:2]
-        kernel, stride, padding = ctx.geom
-        gy = gy.contiguous()
-        if ctx.post_act != "none":
-            gy = ops.act_backward(saved[2], gy, ctx.post_act)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.conv(gy, weight, None, kernel=kernel, stride=stride, padding=padding)  # [Cin, Cout, *k] read as a Conv weight
-            if dx.shape != x.shape:
-                raise ValueError(f"transposed-convolution geometry is not invertible: {tuple(dx.shape)} vs {tuple(x.shape)}")
-        if ctx.needs_input_grad[1]:
-            kt = _tup(kernel, x.dim() - 2)
-            dw = _weight_grad(weight, (weight.shape[0], weight.shape[1], *kt),
-                              lambda out, acc: ops.conv_wgrad(gy, x, kernel, stride, padding, out=out, accumulate=acc))
-        if ctx.needs_input_grad[2]:
-            db = ops.bias_grad(gy).to(ctx.bias_dtype)
-        return dx, dw, db, None, None, None, None, None
+    return _Conv.apply(x, weight, bias, None, res, ConvSpec(1))
 
 
 def conv_transpose(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, kernel, stride, padding,
                    output_padding=0, post_act: str = "none") -> torch.Tensor:
     """post_act(nn.ConvTransposeNd) over an arena tensor (weight [Cin, Cout, *k]); differentiable in x, weight, bias (kernel 3 at stride 1 or 2,
     kernel 4 at stride 2: the VQ-VAE up-sampling); post_act "none" or "relu"."""
-    return _ConvTranspose.apply(x, weight, bias, kernel, stride, padding, output_padding, post_act)
-
-
-def _tap_samples(t: torch.Tensor, out_sp, k, s, p, d):
-    """For every kernel tap the arena tensor `t` ([N, *spatial, C]) sampled at the positions a dilated / strided convolution reads for its output
-    grid `out_sp`: X_tap[n, v, c] = t[n, s v + d tap - p, c], zero outside.  Pure data movement (one zero-padded copy + one strided copy per tap, by
-    torch): the rare dilated layers have no gather kernel of their own -- every multiply-add of their gradients still runs in libgmamd (the 1x1
-    weight-gradient kernel on these samples)."""
-    nsp = len(out_sp)
-    lo = [p[i] for i in range(nsp)]
-    hi = [max(0, s[i] * (out_sp[i] - 1) + d[i] * (k[i] - 1) - p[i] - (t.shape[1 + i] - 1)) for i in range(nsp)]
-    pad = []
-    for i in reversed(range(nsp)):
-        pad += [lo[i], hi[i]]
-    tp = torch.nn.functional.pad(t, [0, 0] + pad)  # (channels last: the first pair pads C by nothing)
-    import itertools
-    for tap in itertools.product(*[range(k[i]) for i in range(nsp)]):
-        idx = [slice(None)] + [slice(d[i] * tap[i], d[i] * tap[i] + s[i] * (out_sp[i] - 1) + 1, s[i]) for i in range(nsp)] + [slice(None)]
-        yield tap, tp[tuple(idx)].contiguous()
-
-
-class _ConvDilated(torch.autograd.Function):
-    """post_act(nn.ConvNd) with dilation > 1 (reference: the VQ-VAE's down-sampling Convolution(dilation=downsample_parameters[i][2]),
-    nets/vqvae.py:127-150).  Forward: the generic kernel.  dx: the transposed convolution with the same weight, stride, padding and dilation.
-    dW: per tap a 1x1 weight gradient (gm_conv_wgrad) of gy against the input sampled where that tap read it."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, kernel, stride, padding, dilation, post_act="none"):
-        y = ops.conv(x, weight, bias, kernel=kernel, stride=stride, padding=padding, dilation=dilation, post_act=post_act)
-        ctx.post_act = post_act
-        if post_act != "none":
-            ctx.save_for_backward(x, weight, y)
-        else:
-            ctx.save_for_backward(x, weight)
-        ctx.geom = (kernel, stride, padding, dilation)
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        saved = ctx.saved_tensors
-        x, weight = saved[:2]
-        kernel, stride, padding, dilation = ctx.geom
-        gy = gy.contiguous()
-        if ctx.post_act != "none":
-            gy = ops.act_backward(saved[2], gy, ctx.post_act)
-        nsp = x.dim() - 2
-        k, s, p, d = _tup(kernel, nsp), _tup(stride, nsp), _tup(padding, nsp), _tup(dilation, nsp)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            opad = tuple(x.shape[1 + i] - ((gy.shape[1 + i] - 1) * s[i] - 2 * p[i] + d[i] * (k[i] - 1) + 1) for i in range(nsp))
-            dx = ops.conv(gy, weight, None, kernel=kernel, stride=stride, padding=padding, dilation=dilation, transposed=True, output_padding=opad)
-        if ctx.needs_input_grad[1]:
-            dw32 = torch.empty((weight.shape[0], weight.shape[1], *k), dtype=torch.float32, device=x.device)
-            for tap, xs in _tap_samples(x, tuple(gy.shape[1:-1]), k, s, p, d):
-                dw32[(slice(None), slice(None)) + tap] = ops.conv_wgrad(xs, gy, 1, 1, 0).reshape(weight.shape[0], weight.shape[1])
-            dw = dw32.to(weight.dtype)
-        if ctx.needs_input_grad[2]:
-            db = ops.bias_grad(gy).to(ctx.bias_dtype)
-        return dx, dw, db, None, None, None, None, None
-
-
-class _ConvTransposeDilated(torch.autograd.Function):
-    """post_act(nn.ConvTransposeNd) with dilation > 1 (the VQ-VAE's up-sampling Convolution(is_transposed=True, dilation=...), nets/vqvae.py:244-261): the
-    adjoint of _ConvDilated with the same weight read as [out = Cin, in = Cout]."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, kernel, stride, padding, output_padding, dilation, post_act="none"):
-        y = ops.conv(x, weight, bias, kernel=kernel, stride=stride, padding=padding, dilation=dilation, transposed=True, output_padding=output_padding,
-                     post_act=post_act)
-        ctx.post_act = post_act
-        if post_act != "none":
-            ctx.save_for_backward(x, weight, y)
-        else:
-            ctx.save_for_backward(x, weight)
-        ctx.geom = (kernel, stride, padding, dilation)
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        saved = ctx.saved_tensors
-        x, weight = saved[:2]
-        kernel, stride, padding, dilation = ctx.geom
-        gy = gy.contiguous()
-        if ctx.post_act != "none":
-            gy = ops.act_backward(saved[2], gy, ctx.post_act)
-        nsp = x.dim() - 2
-        k, s, p, d = _tup(kernel, nsp), _tup(stride, nsp), _tup(padding, nsp), _tup(dilation, nsp)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.conv(gy, weight, None, kernel=kernel, stride=stride, padding=padding, dilation=dilation)  # [Cin, Cout, *k] read as a Conv weight
-            if dx.shape != x.shape:
-                raise ValueError(f"transposed-convolution geometry is not invertible: {tuple(dx.shape)} vs {tuple(x.shape)}")
-        if ctx.needs_input_grad[1]:
-            dw32 = torch.empty((weight.shape[0], weight.shape[1], *k), dtype=torch.float32, device=x.device)
-            for tap, gs in _tap_samples(gy, tuple(x.shape[1:-1]), k, s, p, d):  # gy sampled where the adjoint convolution reads it for every input voxel
-                dw32[(slice(None), slice(None)) + tap] = ops.conv_wgrad(gs, x, 1, 1, 0).reshape(weight.shape[0], weight.shape[1])
-            dw = dw32.to(weight.dtype)
-        if ctx.needs_input_grad[2]:
-            db = ops.bias_grad(gy).to(ctx.bias_dtype)
-        return dx, dw, db, None, None, None, None, None, None
+    return _Conv.apply(x, weight, bias, None, None, ConvSpec(kernel, stride, padding, transposed=True, output_padding=output_padding, post_act=post_act,
+                                                             want_stats=post_act == "none"))
 
 
 def conv_dilated(x, weight, bias=None, *, kernel, stride=1, padding=0, dilation=1, post_act: str = "none") -> torch.Tensor:
     """post_act(conv(x, weight, dilation) + bias) over an arena tensor, differentiable in x, weight, bias; post_act "none" or "relu"."""
-    return _ConvDilated.apply(x, weight, bias, kernel, stride, padding, dilation, post_act)
+    return _Conv.apply(x, weight, bias, None, None, ConvSpec(kernel, stride, padding, dilation=dilation, by_taps=True, post_act=post_act))
 
 
 def conv_transpose_dilated(x, weight, bias=None, *, kernel, stride, padding, output_padding=0, dilation=1, post_act: str = "none") -> torch.Tensor:
     """post_act(nn.ConvTransposeNd with dilation) over an arena tensor (weight [Cin, Cout, *k]), differentiable in x, weight, bias."""
-    return _ConvTransposeDilated.apply(x, weight, bias, kernel, stride, padding, output_padding, dilation, post_act)
+    return _Conv.apply(x, weight, bias, None, None, ConvSpec(kernel, stride, padding, dilation=dilation, transposed=True, output_padding=output_padding,
+                                                             by_taps=True, post_act=post_act))
+
+
+def upsample_conv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    # allow_subpixel=False: the sub-pixel variant pre-sums its weights per parameter version, i.e. on every training step
+    return _Conv.apply(x, weight, bias, None, None, ConvSpec(3, 1, 1, upsample=True, want_stats=True, allow_subpixel=False))
 
 
 class _SigmaFromLogVar(torch.autograd.Function):
@@ -361,38 +267,6 @@ def to_arena(x: torch.Tensor) -> torch.Tensor:
 def from_arena(x: torch.Tensor) -> torch.Tensor:
     """N[D]HWC -> NC[D]HW, differentiable."""
     return _FromArena.apply(x)
-
-
-class _UpsampleConv(torch.autograd.Function):
-    """Nearest 2x upsampling folded into a 3^d stride-1 convolution (reference Upsample, diffusion_model_unet.py:534-586)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        # the folded up-sampling path: the sub-pixel variant pre-sums its weights per parameter version, i.e. on every training step
-        y = ops.conv(x, weight, bias, kernel=3, stride=1, padding=1, upsample=True, allow_subpixel=False, want_stats=True)
-        ctx.save_for_backward(x, weight)
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        gy = gy.contiguous()
-        dx = dw = db = None
-        nsp = x.dim() - 2
-        if ctx.needs_input_grad[0]:
-            du = ops.conv(gy, weight, None, kernel=3, stride=1, padding=1, transposed=True)  # gradient on the upsampled grid
-            dx = ops.scale(ops.resample2x(du, "down"), float(2 ** nsp))                        # sum over each 2^d cell
-        if ctx.needs_input_grad[1]:
-            xu = ops.resample2x(x, "up")
-            dw = _weight_grad(weight, tuple(weight.shape), lambda out, acc: ops.conv_wgrad(xu, gy, 3, 1, 1, out=out, accumulate=acc))
-        if ctx.needs_input_grad[2]:
-            db = ops.bias_grad(gy).to(ctx.bias_dtype)
-        return dx, dw, db
-
-
-def upsample_conv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    return _UpsampleConv.apply(x, weight, bias)
 
 
 class _Activation(torch.autograd.Function):
@@ -620,29 +494,15 @@ class _SiLU(torch.autograd.Function):
     """SiLU of a small (N, L, C) tensor (the timestep-embedding MLP) on the GroupNorm apply / backward kernels with an identity affine."""
 
     @staticmethod
-    def _tables(x):
-        c = x.shape[-1]
-        one = torch.ones((x.shape[0], c), dtype=torch.float32, device=x.device)
-        return one, torch.zeros_like(one)
-
-    @staticmethod
     def forward(ctx, x):
-        one, zero = _SiLU._tables(x)
+        one = torch.ones((x.shape[0], x.shape[-1]), dtype=torch.float32, device=x.device)
         ctx.save_for_backward(x)
-        return ops.gn_apply(x.contiguous(), one, zero, "silu")
+        return ops.gn_apply(x.contiguous(), one, torch.zeros_like(one), "silu")
 
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        x, gy = x.contiguous(), gy.contiguous()
-        one, zero = _SiLU._tables(x)
-        n, c = x.shape[0], x.shape[-1]
-        v = ops.rows_of(x) // max(n, 1)
-        dx = torch.empty_like(x)
-        ops.check(ops.lib().gm_gn_bwd_apply(x.data_ptr(), ops.arena_ld(x), gy.data_ptr(), ops.arena_ld(gy), dx.data_ptr(), ops.arena_ld(dx),
-                                            one.data_ptr(), zero.data_ptr(), c, one.data_ptr(), zero.data_ptr(), zero.data_ptr(), n, v, c, 1,
-                                            ops.dt_code(x.dtype), ops._stream()), "gm_gn_bwd_apply")
-        return dx
+        return ops.act_backward(x, gy, "silu", from_output=False)
 
 
 def silu(x: torch.Tensor) -> torch.Tensor:

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import itertools
 import math
 import os
 import threading
@@ -1792,11 +1793,34 @@ def linear(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch
 # ------------------------------------------------------------------------------------------------------------------------
 # backward kernels (wrapped as torch.autograd.Functions in generativemodels_amd/autograd.py)
 # ------------------------------------------------------------------------------------------------------------------------
+def conv_wgrad_route(nsp: int, kernel: Sequence[int], stride: Sequence[int], pads: Sequence[int], dilation: Sequence[int], by_taps: bool = False,
+                     empty: bool = False, vectors: bool = True) -> str:
+    """Which way ops.conv_wgrad forms a weight gradient over `nsp` spatial axes, the first that holds: "empty" (an operand has no elements: zeros, no
+    launch), "taps" (asked for, or any dilation > 1: per tap a k = 1 gradient over the sampled operand), "phases" (k = 4 at stride 2: _conv_wgrad_k4s2),
+    "padded" (`vectors` false -- a channel count, pitch or pointer that no 16-byte vector serves: channels zero-padded) or "native" (gm_conv_wgrad, which may
+    still refuse the geometry).  "taps", "phases" and "padded" come back here for their inner launches.  Plain facts, no tensors, no library."""
+    taps = by_taps or any(d > 1 for d in dilation)
+    if not taps and (len(set(kernel)) != 1 or len(set(stride)) != 1):
+        raise ValueError("conv_wgrad: kernel and stride must be the same on every axis")
+    if empty:
+        return "empty"
+    if taps:
+        return "taps"
+    if kernel[0] == 4 and stride[0] == 2 and nsp in (2, 3) and all(0 <= v <= 2 for v in pads):
+        return "phases"
+    if not vectors:
+        return "padded"
+    if nsp == 1 and kernel[0] != 1:
+        raise ValueError("conv_wgrad: 1-D convolutions are covered for kernel 1 only")
+    return "native"
+
+
 def conv_wgrad(x: torch.Tensor, gy: torch.Tensor, kernel, stride=1, padding=0, out: Optional[torch.Tensor] = None,
-               accumulate: bool = False) -> torch.Tensor:
+               accumulate: bool = False, dilation=1, by_taps: bool = False) -> torch.Tensor:
     """Weight gradient of y = conv(x, W) (torch.nn.grad.conv*_weight): x, gy arena tensors (N, *spatial, C); returns fp32
     [Cout, Cin, *kernel].  kernel 1 or 3 (the same on every spatial axis), stride 1 or 2, `padding` = low-side pad (the high side
-    is implied by gy's extents).  An empty batch or volume gives zeros (`out` is cleared, or left as it is under `accumulate`)."""
+    is implied by gy's extents); kernel 4 at stride 2 over phase images; any kernel, stride and dilation per tap (`by_taps`, or a dilation
+    above 1).  An empty batch or volume gives zeros (`out` is cleared, or left as it is under `accumulate`)."""
     require_device(x, gy, out)
     nsp = x.dim() - 2
     if nsp < 1 or nsp > 3 or gy.dim() != x.dim() or gy.dtype != x.dtype or gy.shape[0] != x.shape[0]:
@@ -1808,76 +1832,89 @@ def conv_wgrad(x: torch.Tensor, gy: torch.Tensor, kernel, stride=1, padding=0, o
             raise ValueError("per-axis argument has the wrong length")
         return v
 
-    k, s_, p_ = tup(kernel), tup(stride), tup(padding)
-    if len(set(k)) != 1 or len(set(s_)) != 1:
-        raise ValueError("conv_wgrad: kernel and stride must be the same on every axis")
-    if x.numel() == 0 or gy.numel() == 0:
-        # an empty batch (or volume): the sum over no voxels.  Decided here, without a launch -- an empty tensor has no pointer to hand to the library
-        shape = (gy.shape[-1], x.shape[-1], *k)
+    k, s_, p_, dil = tup(kernel), tup(stride), tup(padding), tup(dilation)
+    cin, cout = x.shape[-1], gy.shape[-1]
+    shape = (cout, cin, *k)
+    vec = 16 // x.element_size()
+    empty = x.numel() == 0 or gy.numel() == 0  # (an empty tensor has no pointer to hand to the library, or to ask about)
+    route = conv_wgrad_route(nsp, k, s_, p_, dil, by_taps, empty, empty or not (
+        cin % vec or cout % vec or arena_ld(x) % vec or arena_ld(gy) % vec or x.data_ptr() % 16 or gy.data_ptr() % 16))
+    if out is None and accumulate:
+        raise ValueError("accumulate needs an existing gradient tensor")
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError("conv_wgrad: out must be a contiguous fp32 [Cout, Cin, *kernel] tensor")
+    if route == "empty":  # the sum over no voxels: decided here, without a launch
         if out is None:
-            if accumulate:
-                raise ValueError("accumulate needs an existing gradient tensor")
             return torch.zeros(shape, dtype=torch.float32, device=x.device)
-        if tuple(out.shape) != shape or out.dtype != torch.float32:
-            raise ValueError("conv_wgrad: out must be a contiguous fp32 [Cout, Cin, *kernel] tensor")
         if not accumulate:
             with torch.no_grad():
                 out.zero_()
         return out
-    if k[0] == 4 and s_[0] == 2 and nsp in (2, 3) and all(0 <= v <= 2 for v in p_):
-        return _conv_wgrad_k4s2(x, gy, p_, out, accumulate)
-    vec = 16 // x.element_size()
-    if x.shape[-1] % vec or gy.shape[-1] % vec or arena_ld(x) % vec or arena_ld(gy) % vec or x.data_ptr() % 16 or gy.data_ptr() % 16:
-        # ragged channel counts (the 1-channel input / output convolutions): zero-pad the channels to one 16-byte vector
+    if route == "padded":  # ragged channel counts (the 1-channel input / output convolutions): zero-pad the channels to one 16-byte vector
         def padded(t):
             cp = (t.shape[-1] + vec - 1) // vec * vec
             z = torch.zeros((*t.shape[:-1], cp), dtype=t.dtype, device=t.device)
             copy_channels(t, z[..., :t.shape[-1]])
             return z
-        if accumulate and out is None:
-            raise ValueError("accumulate needs an existing gradient tensor")
-        full = conv_wgrad(padded(x), padded(gy), kernel, stride, padding)
-        res = full[:gy.shape[-1], :x.shape[-1]].contiguous()
+        res = conv_wgrad(padded(x), padded(gy), k, s_, p_)[:cout, :cin]
         if out is None:
-            return res
-        if tuple(out.shape) != tuple(res.shape) or out.dtype != torch.float32:
-            raise ValueError("conv_wgrad: out must be a contiguous fp32 [Cout, Cin, *kernel] tensor")
+            return res.contiguous()
         with torch.no_grad():  # (the two edge convolutions of a network: a few thousand elements)
             out.add_(res) if accumulate else out.copy_(res)
         return out
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if route == "taps":  # per tap a k = 1 weight gradient of gy against x sampled where that tap read it
+        with torch.no_grad():
+            for tap, xs in _tap_samples(x, tuple(gy.shape[1:-1]), k, s_, p_, dil):
+                dst, src = out[(slice(None), slice(None)) + tap], conv_wgrad(xs, gy, 1, 1, 0).reshape(cout, cin)
+                dst.add_(src) if accumulate else dst.copy_(src)
+    elif route == "phases":
+        _conv_wgrad_k4s2(x, gy, p_, out, accumulate)
+    else:
+        _conv_wgrad_native(x, gy, k, s_, p_, out, accumulate)
+    return out
+
+
+def _conv_wgrad_native(x, gy, k, s, p, out, accumulate):
+    """gm_conv_wgrad over operands it reads in 16-byte vectors, into `out` (onto it under `accumulate`); ValueError where it has no kernel."""
+    nsp = x.dim() - 2
     cin, cout = x.shape[-1], gy.shape[-1]
     d = GmWgradDesc()
     d.x, d.x_ld, d.gy, d.gy_ld = x.data_ptr(), arena_ld(x), gy.data_ptr(), arena_ld(gy)
     d.N, d.Cin, d.Cout = x.shape[0], cin, cout
-    src = (1,) * (3 - nsp) + tuple(x.shape[1:-1])
-    dst = (1,) * (3 - nsp) + tuple(gy.shape[1:-1])
-    d.Ds, d.Hs, d.Ws = src
-    d.Do, d.Ho, d.Wo = dst
-    kk = (1,) * (3 - nsp) + k
-    if nsp == 1 and k[0] != 1:
-        raise ValueError("conv_wgrad: 1-D convolutions are covered for kernel 1 only")
-    d.kd, d.kh, d.kw = kk
-    d.stride = s_[0]
-    d.pd, d.ph, d.pw = (0,) * (3 - nsp) + p_
+    d.Ds, d.Hs, d.Ws = (1,) * (3 - nsp) + tuple(x.shape[1:-1])
+    d.Do, d.Ho, d.Wo = (1,) * (3 - nsp) + tuple(gy.shape[1:-1])
+    d.kd, d.kh, d.kw = (1,) * (3 - nsp) + k
+    d.stride = s[0]
+    d.pd, d.ph, d.pw = (0,) * (3 - nsp) + p
     d.dtype, d.accumulate = dt_code(x.dtype), int(accumulate)
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate needs an existing gradient tensor")
-        out = torch.empty((cout, cin, *k), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (cout, cin, *k) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("conv_wgrad: out must be a contiguous fp32 [Cout, Cin, *kernel] tensor")
     d.dw = out.data_ptr()
     ws_bytes = lib().gm_conv_wgrad_workspace_bytes(C.byref(d))
     if ws_bytes < 0:
         raise ValueError("conv_wgrad: geometry not covered (kernel 1 or 3, stride 1 or 2, channel counts multiples of a 16-byte vector)")
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws_bytes
-    taps = math.prod(k)
     nvo = gy.shape[0] * math.prod(gy.shape[1:-1])
-    _timed(f"conv_wgrad<{str(x.dtype).split('.')[-1]}>", dict(flops=2.0 * nvo * cin * cout * taps, bytes=float(x.element_size() * (x.numel() + gy.numel())),
-                                                          shape=f"{cin}->{cout} k{k} s{s_} out{tuple(gy.shape[1:-1])}"),
+    _timed(f"conv_wgrad<{str(x.dtype).split('.')[-1]}>", dict(flops=2.0 * nvo * cin * cout * math.prod(k), bytes=float(x.element_size() * (x.numel() + gy.numel())),
+                                                          shape=f"{cin}->{cout} k{k} s{s} out{tuple(gy.shape[1:-1])}"),
            lambda: check(lib().gm_conv_wgrad(C.byref(d), _stream()), "gm_conv_wgrad"))
-    return out
+
+
+def _tap_samples(t: torch.Tensor, out_sp, k, s, p, d):
+    """For every kernel tap the arena tensor `t` ([N, *spatial, C]) sampled at the positions a dilated / strided convolution reads for its output
+    grid `out_sp`: X_tap[n, v, c] = t[n, s v + d tap - p, c], zero outside.  Pure data movement (one zero-padded copy + one strided copy per tap, by
+    torch): the rare dilated layers have no gather kernel of their own -- every multiply-add of their gradients still runs in libgmamd (the 1x1
+    weight-gradient kernel on these samples)."""
+    nsp = len(out_sp)
+    hi = [max(0, s[i] * (out_sp[i] - 1) + d[i] * (k[i] - 1) - p[i] - (t.shape[1 + i] - 1)) for i in range(nsp)]
+    pad = []
+    for i in reversed(range(nsp)):
+        pad += [p[i], hi[i]]
+    tp = torch.nn.functional.pad(t, [0, 0] + pad)  # (channels last: the first pair pads C by nothing)
+    for tap in itertools.product(*[range(k[i]) for i in range(nsp)]):
+        idx = [slice(None)] + [slice(d[i] * tap[i], d[i] * tap[i] + s[i] * (out_sp[i] - 1) + 1, s[i]) for i in range(nsp)] + [slice(None)]
+        yield tap, tp[tuple(idx)].contiguous()
 
 
 def stride2_phase_taps(pad: int) -> dict:
@@ -1896,20 +1933,11 @@ def stride2_phase_taps(pad: int) -> dict:
 
 
 def _conv_wgrad_k4s2(x, gy, pads, out, accumulate):
-    """Weight gradient of a k = 4 / stride-2 convolution (the VQ-VAE down-sampling convolutions and, with the operands exchanged, its
+    """Into `out` (onto it under `accumulate`) the weight gradient of a k = 4 / stride-2 convolution (the VQ-VAE down-sampling convolutions and, with the operands exchanged, its
     ConvTranspose up-sampling: vqvae.py:127-150,244-261) from the MFMA weight-gradient kernel of 3-tap stride-1 convolutions: per tap-parity
     class r (2^d of them) ONE launch over the phase image x[rho::2] (gm_phase2x) yields the 2^d taps k = 2 j + r of that class as a sub-block of
     its 3^d result (stride2_phase_taps).  27/8 of the minimal multiply-adds on a 600-700 TFLOP/s kernel; fixed-order sums (deterministic)."""
     nsp = x.dim() - 2
-    cin, cout = x.shape[-1], gy.shape[-1]
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate needs an existing gradient tensor")
-        res = torch.empty((cout, cin) + (4,) * nsp, dtype=torch.float32, device=x.device)
-    else:
-        if tuple(out.shape) != (cout, cin) + (4,) * nsp or out.dtype != torch.float32:
-            raise ValueError("conv_wgrad: out must be a contiguous fp32 [Cout, Cin, *kernel] tensor")
-        res = out
     taps = [stride2_phase_taps(p) for p in pads]
     with torch.no_grad():
         for cls in range(1 << nsp):
@@ -1917,16 +1945,16 @@ def _conv_wgrad_k4s2(x, gy, pads, out, accumulate):
             xp = phase2x(x, [taps[a][r[a]][0] for a in range(nsp)])
             g3 = conv_wgrad(xp, gy, 3, 1, 1)  # [Cout, Cin, 3 (x nsp)]
             src = g3[(slice(None), slice(None)) + tuple(slice(taps[a][r[a]][1], taps[a][r[a]][2] + 1) for a in range(nsp))]
-            dst = res[(slice(None), slice(None)) + tuple(slice(r[a], 4, 2) for a in range(nsp))]
+            dst = out[(slice(None), slice(None)) + tuple(slice(r[a], 4, 2) for a in range(nsp))]
             # (the 2^d strided sub-blocks of a [Cout, Cin, 4, 4(, 4)] tensor: a scatter of the kernel's outputs into the parameter layout)
-            dst.add_(src) if (accumulate and out is not None) else dst.copy_(src)
-    return res
+            dst.add_(src) if accumulate else dst.copy_(src)
 
 
-def act_backward(y: torch.Tensor, gy: torch.Tensor, act: str) -> torch.Tensor:
+def act_backward(y: torch.Tensor, gy: torch.Tensor, act: str, from_output: bool = True) -> torch.Tensor:
     """gy * act'(z) from the activation's OUTPUT y = act(z) for activations whose derivative is a function of the output sign: ReLU
-    (y > 0 <=> z > 0).  The fused convolution epilogues store only y; this is the first step of their backward."""
-    if act not in ("relu", "leakyrelu"):
+    (y > 0 <=> z > 0).  The fused convolution epilogues store only y; this is the first step of their backward.  from_output=False: `y` is
+    the PRE-activation z, which is what SiLU is differentiated from (autograd.silu)."""
+    if act not in (("relu", "leakyrelu") if from_output else ("silu",)):
         raise NotImplementedError(f"activation '{act}' has no backward kernel (training covers none / relu / leakyrelu epilogues)")
     require_device(y, gy)
     if y.shape != gy.shape or y.dtype != gy.dtype:
