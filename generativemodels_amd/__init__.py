@@ -26,7 +26,7 @@ def __getattr__(name):
         return GraphedForwardBackward
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
-_MIRRORED = ["", ".networks", ".networks.nets", ".networks.nets.patchgan_discriminator", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",
+_MIRRORED = ["", ".networks", ".networks.nets", ".networks.nets.diffusion_model_unet", ".networks.nets.patchgan_discriminator", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",
              ".inferers", ".utils", ".metrics", ".losses", ".losses.adversarial_loss"]
 
 

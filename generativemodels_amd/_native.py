@@ -225,6 +225,11 @@ PROTOTYPES = {
     "gm_bn_bwd_finalize": (C.c_int, [c_vp, C.c_int, C.c_int, c_ll, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gm_bn_bwd_apply": (C.c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_float, C.c_int, c_vp]),
     "gm_patch_adv_loss": (C.c_int, [c_vp, c_ll, C.c_int, C.c_int, C.c_float, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp]),
+    "gm_head_chunk": (C.c_int, [C.c_int]),
+    "gm_head_hidden": (C.c_int, [c_vp, c_ll, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
+    "gm_head_tail": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
+    "gm_head_dinput": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
+    "gm_head_dparams": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + [C.c_int] * 7 + [c_vp]),
 }
 
 _lib = None

@@ -28,6 +28,8 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
   patch_adv_loss  PatchAdversarialLoss over one discriminator output: activation, criterion, reduction and gradient in gm_patch_adv_loss
   ssim_cs / ms_ssim_factors   (NC[D]HW images, not arenas) the SSIM / cs means and maps, the MS-SSIM factors; backward: gm_ssim_cs_backward per scale,
                   from the coarsest up, each scale's gradient folded into the next finer scale's store
+  classifier_head the DiffusionModelEncoder head Linear -> ReLU -> dropout mask -> Linear on the arena (gm_head_hidden + gm_head_tail); backward:
+                  gm_head_tail (da from the logit gradient), gm_head_dinput, and gm_head_dparams only where a parameter asks for its gradient
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -40,7 +42,7 @@ import torch
 
 from . import ops
 
-__all__ = ["ssim_cs", "ms_ssim_factors", "cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["classifier_head", "ssim_cs", "ms_ssim_factors", "cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -971,3 +973,30 @@ class _MsSsimFactors(torch.autograd.Function):
 def ms_ssim_factors(x: torch.Tensor, y: torch.Tensor, taps, c1: float, c2: float, scales: int) -> torch.Tensor:
     """(scales, batch) fp32: relu and the product of powers over them stay torch arithmetic, which torch differentiates."""
     return _MsSsimFactors.apply(x, y, taps, float(c1), float(c2), int(scales))
+
+
+class _ClassifierHead(torch.autograd.Function):
+    """logits = W2 (relu(W1 flatten(h) + b1) * mask) + b2 over the arena h (ops.classifier_head); keeps h and the hidden activations a."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, mask):
+        r = ops.classifier_head(h, w1, b1, w2, b2, mask)
+        ctx.save_for_backward(h, w1, w2, r.a, *(() if mask is None else (mask,)))
+        ctx.dtypes = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
+        return r.logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        h, w1, w2, a, *mask = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dh, grads = ops.classifier_head_backward(h, a, mask[0] if mask else None, w1, w2, g=g.contiguous(), want_input=need[0], want_params=need[1:5])
+        return (dh, *(None if t is None else t.to(d) for t, d in zip(grads, ctx.dtypes)), None)
+
+
+def classifier_head(h: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: torch.Tensor, b2: Optional[torch.Tensor],
+                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The classifier head of DiffusionModelEncoder over the arena tensor h (N, *spatial, C): Linear(F, H) with W1's columns in the reference's flatten
+    order of N C [D] H W, ReLU, an optional (N, H) multiplier (the dropout mask), Linear(H, K) -> logits (N, K).  Differentiable in h and the four
+    parameters; the parameter-gradient kernel runs only where one of them requires grad."""
+    return _ClassifierHead.apply(h, w1, b1, w2, b2, mask)

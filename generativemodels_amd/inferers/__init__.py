@@ -1,5 +1,6 @@
 from .inferer import (ControlNetDiffusionInferer, ControlNetLatentDiffusionInferer, DiffusionInferer, LatentDiffusionInferer,
                       VQVAETransformerInferer)
+from .guidance import classifier_guidance_gradient
 
 __all__ = ["DiffusionInferer", "LatentDiffusionInferer", "ControlNetDiffusionInferer", "ControlNetLatentDiffusionInferer",
-           "VQVAETransformerInferer"]
+           "VQVAETransformerInferer", "classifier_guidance_gradient"]

@@ -18,6 +18,7 @@ at the reference's three places per transformer block (after `to_out`, after GEG
 precision: fp32 parameters under `generativemodels_amd.autocast(torch.bfloat16)` (or torch.autocast("cuda")) compute in bf16."""
 from __future__ import annotations
 
+import copy
 import math
 from typing import Optional, Sequence
 
@@ -27,7 +28,7 @@ import torch.nn as nn
 from ... import ops
 from ._blocks import SPADEResnetBlock, AttentionBlock, ConvP, ResnetBlock, ensure_tuple_rep, gn_prologue, lin, tokens, wants_grad, zero_module
 
-__all__ = ["DiffusionModelUNet"]
+__all__ = ["DiffusionModelUNet", "DiffusionModelEncoder"]
 
 
 def _dropout(x: torch.Tensor, p: float) -> torch.Tensor:
@@ -614,3 +615,200 @@ def _add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a + b for two dense arena tensors of the same shape (ControlNet residual hook, diffusion_model_unet.py:1917-1932)."""
     ones = torch.ones(a.shape[0], dtype=torch.float32, device=a.device)
     return ops.axpby_rows(a, b, ones, ones)
+
+
+def _detached_clone(module: nn.Module) -> nn.Module:
+    """A structural copy of `module` whose parameters are `p.detach()` views of the original's: same storage and version counters, no grad.  The original
+    is not touched (nothing global changes: another thread, an optimizer or a hook sees its parameters as they are)."""
+    clone = copy.copy(module)
+    clone.__dict__.pop("_detached_view", None)
+    clone._parameters = {k: (None if q is None else q.detach()) for k, q in module._parameters.items()}
+    clone._modules = {k: (None if m is None else _detached_clone(m)) for k, m in module._modules.items()}
+    return clone
+
+
+def _detached_view(module: nn.Module) -> nn.Module:
+    """`module` with its parameters handed over as detached tensors -- constants of the graph a forward through it records.  The autograd Functions consult
+    `needs_input_grad`, so a backward through that graph runs the data-gradient kernels only: no weight, bias or affine gradient is computed and thrown
+    away (classifier guidance asks for d log p / d x hundreds of times per image).  The view is kept on the module and rebuilt when a parameter has moved
+    (`.to()`, `.cuda()`); in-place updates (an optimizer step, load_state_dict) are seen through the shared storage, and the derived-weight caches of
+    `ops`, keyed by tensor identity and version, stay warm across calls."""
+    key = tuple((q.data_ptr(), q.dtype, q.device) for q in module.parameters())
+    ent = module.__dict__.get("_detached_view")
+    if ent is None or ent[0] != key:
+        ent = (key, _detached_clone(module))
+        module.__dict__["_detached_view"] = ent  # (through __dict__: not a registered sub-module, not part of the state_dict)
+    for a, b in zip(module.modules(), ent[1].modules()):
+        b.training = a.training
+    return ent[1]
+
+
+class DiffusionModelEncoder(_TimestepPath, nn.Module):
+    """Drop-in for generative.networks.nets.diffusion_model_unet.DiffusionModelEncoder (reference :1946-2116; same arguments, state_dict keys and
+    forward): the noise-aware classifier of Wolleb et al., "Diffusion Models for Medical Anomaly Detection" -- the UNet's encoder half (every level
+    downsamples, the last one included; no middle block) and the head Linear(4096, 512) -> ReLU -> Dropout(0.1) -> Linear(512, out_channels).
+
+    The encoder levels are the `_Stage`s of DiffusionModelUNet / ControlNet, run by the same fused kernels (`run`) and the same native backward
+    (`run_train`).  The head reads the channels-last arena directly (csrc/classifier_head.hip): `out.0.weight` keeps the reference's (channel, voxel)
+    column order and is never permuted.  `forward` under torch.no_grad(), or in eval() with an input that does not require grad, is the fused inference
+    path; train() mode or an input that requires grad take the differentiable one (`_blocks.wants_grad`).  In eval() with an input that requires grad
+    -- the classifier-guidance loop -- the parameters are handed to the kernels detached (`_detached_view`), so the backward computes the input gradient only."""
+
+    HEAD_FEATURES = 4096
+
+    def __init__(self, spatial_dims: int, in_channels: int, out_channels: int, num_res_blocks: Sequence[int] | int = (2, 2, 2, 2),
+                 num_channels: Sequence[int] = (32, 64, 64, 64), attention_levels: Sequence[bool] = (False, False, True, True),
+                 norm_num_groups: int = 32, norm_eps: float = 1e-6, resblock_updown: bool = False,
+                 num_head_channels: int | Sequence[int] = 8, with_conditioning: bool = False, transformer_num_layers: int = 1,
+                 cross_attention_dim: int | None = None, num_class_embeds: int | None = None, upcast_attention: bool = False) -> None:
+        super().__init__()
+        if with_conditioning is True and cross_attention_dim is None:
+            raise ValueError("DiffusionModelEncoder expects dimension of the cross-attention conditioning (cross_attention_dim) "
+                             "when using with_conditioning.")
+        if cross_attention_dim is not None and with_conditioning is False:
+            raise ValueError("DiffusionModelEncoder expects with_conditioning=True when specifying the cross_attention_dim.")
+        if any((c % norm_num_groups) != 0 for c in num_channels):
+            raise ValueError("DiffusionModelEncoder expects all num_channels being multiple of norm_num_groups")
+        if len(num_channels) != len(attention_levels):
+            raise ValueError("DiffusionModelEncoder expects num_channels being same size of attention_levels")
+        if isinstance(num_head_channels, int):
+            num_head_channels = ensure_tuple_rep(num_head_channels, len(attention_levels))
+        if len(num_head_channels) != len(attention_levels):
+            raise ValueError("num_head_channels should have the same length as attention_levels. For the i levels without attention,"
+                             " i.e. `attention_level[i]=False`, the num_head_channels[i] will be ignored.")
+        if isinstance(num_res_blocks, int):  # (the reference indexes num_res_blocks and fails on an int)
+            num_res_blocks = ensure_tuple_rep(num_res_blocks, len(num_channels))
+        if len(num_res_blocks) != len(num_channels):
+            raise ValueError("`num_res_blocks` should be a single integer or a tuple of integers with the same length as "
+                             "`num_channels`.")
+        self.spatial_dims = spatial_dims
+        self.in_channels = in_channels
+        self.block_out_channels = tuple(num_channels)
+        self.out_channels = out_channels
+        self.num_res_blocks = tuple(num_res_blocks)
+        self.attention_levels = tuple(attention_levels)
+        self.num_head_channels = tuple(num_head_channels)
+        self.with_conditioning = with_conditioning
+        self.num_class_embeds = num_class_embeds
+        self.resblock_updown = resblock_updown
+        ted = num_channels[0] * 4
+
+        self.conv_in = ConvP(spatial_dims, in_channels, num_channels[0], 3, 1, 1)
+        self.time_embed = nn.Sequential(nn.Linear(num_channels[0], ted), nn.SiLU(), nn.Linear(ted, ted))
+        if num_class_embeds is not None:
+            self.class_embedding = nn.Embedding(num_class_embeds, ted)
+        self.down_blocks = nn.ModuleList()
+        out_c = num_channels[0]
+        for i in range(len(num_channels)):
+            in_c, out_c = out_c, num_channels[i]
+            io = [(in_c if j == 0 else out_c, out_c) for j in range(num_res_blocks[i])]
+            # every level downsamples: the reference's `is_final_block` is never true (:2049)
+            self.down_blocks.append(_Stage(spatial_dims, io, ted, norm_num_groups, norm_eps, attention_levels[i], cond=with_conditioning,
+                                           heads_ch=num_head_channels[i], nlayers=transformer_num_layers, cross_dim=cross_attention_dim,
+                                           upcast=upcast_attention, dropout=0.0, resampler="downsampler", resblock_updown=resblock_updown,
+                                           out_channels=out_c))
+        self.out = nn.Sequential(nn.Linear(self.HEAD_FEATURES, 512), nn.ReLU(), nn.Dropout(0.1), nn.Linear(512, self.out_channels))
+
+    def supports_training(self) -> bool:
+        return True
+
+    # ---- checks (nothing is launched before they pass) -----------------------------------------------------------------------
+    def _feature_shape(self, spatial: Sequence[int]) -> tuple:
+        """Spatial extents of the last level's output: a strided 3^d convolution with padding 1 per level, or the 2x average pool of a
+        resblock_updown level."""
+        for _ in self.down_blocks:
+            spatial = [n // 2 if self.resblock_updown else (n - 1) // 2 + 1 for n in spatial]
+        return tuple(spatial)
+
+    def _check(self, x: torch.Tensor, timesteps: torch.Tensor, context, class_labels) -> None:
+        if context is not None and self.with_conditioning is False:
+            raise ValueError("model should have with_conditioning = True if context is provided")
+        if self.num_class_embeds is not None and class_labels is None:
+            raise ValueError("class_labels should be provided when num_class_embeds > 0")
+        if x.dim() != self.spatial_dims + 2 or x.shape[1] != self.in_channels:
+            raise ValueError(f"expected input of shape (N, {self.in_channels}, *{self.spatial_dims} spatial dims), got {tuple(x.shape)}")
+        if timesteps.ndim != 1 or timesteps.shape[0] not in (1, x.shape[0]):
+            raise ValueError("timesteps must be 1-D with one entry, or one per batch element")
+        count = self.block_out_channels[-1] * math.prod(self._feature_shape(x.shape[2:]))
+        if count != self.out[0].in_features:
+            raise ValueError(f"DiffusionModelEncoder: an input of shape {tuple(x.shape)} leaves {count} features after the last level, the head "
+                             f"Linear expects {self.out[0].in_features}")
+
+    # ---- the encoder half -> the arena tensor (N, *spatial, C) of the last level ------------------------------------------------
+    def _encode_arena(self, x, timesteps, context, class_labels) -> torch.Tensor:
+        """Fused inference path (no gradients)."""
+        ops.require_device(x)
+        x = ops.entry_cast(x, self.conv_in.conv.weight.dtype)
+        with torch.no_grad():
+            rows = self._temb_rows(timesteps.to(x.device), class_labels)
+            if context is not None:
+                ops.require_device(context)
+                context = ops.cast(context.contiguous(), x.dtype)
+            h = self.conv_in.run(ops.to_channels_last(x), want_stats=True)
+            for st in self.down_blocks:
+                for j, rb in enumerate(st.resnets):
+                    h = st.attend(j, rb.run(h, rows[id(rb)]), context)
+                ds = st.downsampler
+                h = ds.run(h, rows[id(ds)]) if isinstance(ds, ResnetBlock) else ds.run(h)
+            return h
+
+    def _encode_arena_train(self, x, timesteps, context, class_labels) -> torch.Tensor:
+        """Differentiable path: native kernels in both directions (generativemodels_amd.autograd)."""
+        from ... import autograd as A
+
+        x, dtype = _train_entry(self, x)
+        emb = _train_timestep_embedding(self, timesteps, class_labels, dtype, x.device, x.shape[0])
+        if context is not None:
+            ops.require_device(context)
+            context = ops.cast(context.contiguous(), dtype)
+        ci = self.conv_in.conv
+        h = A.conv(A.to_arena(x), ci.weight, ci.bias, kernel=3, stride=1, padding=1)
+        # (the down-block walk of _train_encoder, without its skip list and middle block; _train_encoder itself is left as it was: see DESIGN 4.13)
+        for st in self.down_blocks:
+            for j, rb in enumerate(st.resnets):
+                h = rb.run_train(h, emb)
+                if st.attentions is not None:
+                    h = _train_attend(st.attentions[j], h, context)
+            h = _train_resample(st.downsampler, h, emb)
+        return h
+
+    def _input_only(self) -> bool:
+        """eval() mode (the guidance loop), or nothing trainable: a recorded graph differentiates with respect to the input alone."""
+        return not self.training or not any(p.requires_grad for p in self.parameters())
+
+    def _encode(self, x: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor | None = None,
+                class_labels: torch.Tensor | None = None) -> torch.Tensor:
+        """The final feature map as N C [D] H W (what the reference flattens), on the path `forward` would take."""
+        from ... import autograd as A
+
+        self._check(x, timesteps, context, class_labels)
+        if not wants_grad(self, x):
+            return ops.to_channels_first(self._encode_arena(x, timesteps, context, class_labels))
+        net = _detached_view(self) if self._input_only() else self
+        return A.from_arena(net._encode_arena_train(x, timesteps, context, class_labels))
+
+    def _dropout_mask(self, n: int, dtype, device) -> Optional[torch.Tensor]:
+        """train() with p > 0: torch's own dropout op and generator on a tensor of ones, drawn once per forward (the autograd Function keeps it)."""
+        drop = self.out[2]
+        if not (self.training and drop.p > 0.0):
+            return None
+        import torch.nn.functional as F
+
+        return F.dropout(torch.ones(n, self.out[0].out_features, device=device, dtype=dtype), drop.p, True)
+
+    def forward(self, x: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor | None = None,
+                class_labels: torch.Tensor | None = None) -> torch.Tensor:
+        """x: (N, C, *spatial); timesteps: (N,) or (1,), float or integer; context: (N, L_ctx, cross_attention_dim); class_labels: (N,).
+        Returns the logits (N, out_channels) in the compute dtype."""
+        from ... import autograd as A
+
+        self._check(x, timesteps, context, class_labels)
+        if not wants_grad(self, x):
+            l0, l3 = self.out[0], self.out[3]
+            h = self._encode_arena(x, timesteps, context, class_labels)
+            with torch.no_grad():
+                return ops.classifier_head(h, l0.weight, l0.bias, l3.weight, l3.bias, self._dropout_mask(h.shape[0], h.dtype, h.device)).logits
+        net = _detached_view(self) if self._input_only() else self  # (input only: the parameters go in detached)
+        l0, l3 = net.out[0], net.out[3]
+        h = net._encode_arena_train(x, timesteps, context, class_labels)
+        return A.classifier_head(h, l0.weight, l0.bias, l3.weight, l3.bias, self._dropout_mask(h.shape[0], h.dtype, h.device))

@@ -852,6 +852,134 @@ def patch_adv_loss(x: torch.Tensor, criterion: str, target: float, activation: b
     return (value, dx) if want_value and want_grad else (value if want_value else dx)
 
 
+# ---- the classifier head of DiffusionModelEncoder: csrc/classifier_head.hip.  Linear(F, H) -> ReLU -> Dropout -> Linear(H, K) on the arena; W1 stays in the
+# reference's (channel, voxel) column order and is never copied -- the activations are transposed through LDS. ------------------------------------------------
+HeadResult = namedtuple("HeadResult", "logits a logp da")
+
+
+def classifier_head_chunk(dtype: torch.dtype) -> int:
+    """Samples one launch of the head kernels holds in LDS (larger batches loop over chunks): a host entry, no GPU needed."""
+    return int(lib().gm_head_chunk(dt_code(dtype)))
+
+
+def _head_operands(h: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor):
+    """-> (N, S, C, H, K) of the arena h (N, *spatial, C), W1 (H, S * C) and W2 (K, H), validated."""
+    require_device(h, w1, w2)
+    if h.dim() < 3:
+        raise ValueError("classifier_head: h is an arena tensor (N, *spatial, C)")
+    n, c = int(h.shape[0]), int(h.shape[-1])
+    s = rows_of(h) // max(n, 1)
+    if w1.dim() != 2 or w1.shape[1] != s * c or not w1.is_contiguous():
+        raise ValueError(f"classifier_head: W1 must be a contiguous (H, {s * c}) matrix, got {tuple(w1.shape)}")
+    if w2.dim() != 2 or w2.shape[1] != w1.shape[0] or not w2.is_contiguous():
+        raise ValueError(f"classifier_head: W2 must be a contiguous (K, {w1.shape[0]}) matrix, got {tuple(w2.shape)}")
+    if w1.dtype != w2.dtype or (h.dtype, w1.dtype) not in ((torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32)):
+        raise TypeError(f"classifier_head: activations {h.dtype} with parameters {w1.dtype} / {w2.dtype} are not served "
+                        "(fp32 / fp32, bf16 / bf16, or bf16 activations with fp32 parameters)")
+    if n < 1:
+        raise ValueError("classifier_head: empty batch")
+    return n, s, c, int(w1.shape[0]), int(w2.shape[0])
+
+
+def _head_vec(t: Optional[torch.Tensor], shape, dtype, what: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    require_device(t)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+        raise ValueError(f"classifier_head: {what} must be {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}")
+    return t.detach().contiguous()
+
+
+def _head_meta(h, w1, n, k, hid, passes=1):
+    return dict(flops=2.0 * n * (w1.numel() + k * hid), bytes=float(passes * w1.numel() * w1.element_size() + h.numel() * h.element_size()),
+                shape=f"N{n} F{w1.shape[1]} H{hid} K{k}")
+
+
+def classifier_head(h: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: torch.Tensor, b2: Optional[torch.Tensor],
+                    mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, want_da: bool = False) -> HeadResult:
+    """logits = W2 (relu(W1 flatten(h) + b1) * mask) + b2 for the arena h (N, *spatial, C); W1's columns are in the reference's flatten order of
+    N C [D] H W.  Two launches: gm_head_hidden (a, kept for the backward) and gm_head_tail.  mask: (N, H) multiplier in the dtype of h (dropout).
+    labels (N, int64): also logp[n] = log_softmax(logits[n])[labels[n]] (fp32) and, with want_da, da = d(sum logp) / da (fp32, (N, H)) from the
+    same launch.  -> HeadResult(logits (N, K) in the dtype of h, a (N, H), logp, da)."""
+    n, s, c, hid, k = _head_operands(h, w1, w2)
+    b1 = _head_vec(b1, (hid,), w1.dtype, "b1")
+    b2 = _head_vec(b2, (k,), w2.dtype, "b2")
+    mask = _head_vec(mask, (n, hid), h.dtype, "mask")
+    if want_da and labels is None:
+        raise ValueError("classifier_head: da needs labels")
+    if labels is not None:
+        require_device(labels)
+        if tuple(labels.shape) != (n,) or labels.dtype != torch.int64:
+            raise ValueError(f"classifier_head: labels must be ({n},) int64")
+        labels = labels.contiguous()
+    w1, w2 = w1.detach(), w2.detach()
+    a = torch.empty((n, hid), dtype=h.dtype, device=h.device)
+    logits = torch.empty((n, k), dtype=h.dtype, device=h.device)
+    logp = torch.empty((n,), dtype=torch.float32, device=h.device) if labels is not None else None
+    da = torch.empty((n, hid), dtype=torch.float32, device=h.device) if want_da else None
+    name = f"{str(h.dtype).split('.')[-1]},{str(w1.dtype).split('.')[-1]}"
+    passes = -(-n // classifier_head_chunk(h.dtype))
+    _timed(f"head_hidden<{name}>", _head_meta(h, w1, n, 0, hid, passes),
+           lambda: check(lib().gm_head_hidden(h.data_ptr(), arena_ld(h), n, s, c, w1.data_ptr(), _ptr(b1), _ptr(mask), a.data_ptr(), hid, dt_code(h.dtype),
+                                              dt_code(w1.dtype), _stream()), "gm_head_hidden"))
+    _timed(f"head_tail<{name}>", dict(flops=2.0 * n * k * hid, bytes=float(w2.numel() * w2.element_size()), shape=f"N{n} H{hid} K{k}"),
+           lambda: check(lib().gm_head_tail(a.data_ptr(), w2.data_ptr(), _ptr(b2), _ptr(labels), None, logits.data_ptr(), _ptr(logp), _ptr(da), n, hid, k,
+                                            dt_code(h.dtype), dt_code(w2.dtype), _stream()), "gm_head_tail"))
+    return HeadResult(logits, a, logp, da)
+
+
+def classifier_head_backward(h: torch.Tensor, a: torch.Tensor, mask: Optional[torch.Tensor], w1: torch.Tensor, w2: torch.Tensor, g: Optional[torch.Tensor] = None,
+                             da: Optional[torch.Tensor] = None, want_input: bool = True, want_params: Sequence[bool] = (False, False, False, False),
+                             out: Optional[Sequence[Optional[torch.Tensor]]] = None, accumulate: bool = False):
+    """The head's backward from g = d loss / d logits ((N, K), the dtype of h) or from a ready da (fp32 (N, H): classifier_head(labels, want_da)).
+    -> (dh, (dW1, db1, dW2, db2)): dh in arena layout and the dtype of h (gm_head_dinput; None unless want_input), the parameter gradients fp32,
+    dW1 in the reference's column order (gm_head_dparams; only those want_params asks for -- dW2 / db2 need g).  out: four fp32 tensors (or None
+    each) to write, or with accumulate to add, the parameter gradients into."""
+    n, s, c, hid, k = _head_operands(h, w1, w2)
+    a = _head_vec(a, (n, hid), h.dtype, "a")
+    mask = _head_vec(mask, (n, hid), h.dtype, "mask")
+    g = _head_vec(g, (n, k), h.dtype, "g")
+    da = _head_vec(da, (n, hid), torch.float32, "da")
+    if (g is None) == (da is None):
+        raise ValueError("classifier_head_backward: exactly one of g (the logit gradient) and da")
+    want_params = tuple(bool(w) for w in want_params)
+    if (want_params[2] or want_params[3]) and g is None:
+        raise ValueError("classifier_head_backward: dW2 / db2 need g")
+    w1, w2 = w1.detach(), w2.detach()
+    name = f"{str(h.dtype).split('.')[-1]},{str(w1.dtype).split('.')[-1]}"
+    if da is None:
+        da = torch.empty((n, hid), dtype=torch.float32, device=h.device)
+        _timed(f"head_tail<{name},dlogits>", dict(flops=2.0 * n * k * hid, bytes=float(w2.numel() * w2.element_size()), shape=f"N{n} H{hid} K{k}"),
+               lambda: check(lib().gm_head_tail(None, w2.data_ptr(), None, None, g.data_ptr(), None, None, da.data_ptr(), n, hid, k, dt_code(h.dtype),
+                                                dt_code(w2.dtype), _stream()), "gm_head_tail"))
+    dh = None
+    passes = -(-n // classifier_head_chunk(h.dtype))
+    if want_input:
+        dh = torch.empty(h.shape, dtype=h.dtype, device=h.device)
+        _timed(f"head_dinput<{name}>", _head_meta(h, w1, n, 0, hid, passes),
+               lambda: check(lib().gm_head_dinput(da.data_ptr(), a.data_ptr(), _ptr(mask), w1.data_ptr(), dh.data_ptr(), arena_ld(dh), n, s, c, hid,
+                                                  dt_code(h.dtype), dt_code(w1.dtype), _stream()), "gm_head_dinput"))
+    grads = [None, None, None, None]
+    if any(want_params):
+        shapes = ((hid, s * c), (hid,), (k, hid), (k,))
+        for i, (want, shape) in enumerate(zip(want_params, shapes)):
+            if not want:
+                continue
+            t = None if out is None else out[i]
+            if t is None:
+                if accumulate:
+                    raise ValueError("classifier_head_backward: accumulate needs the tensors to add into")
+                t = torch.empty(shape, dtype=torch.float32, device=h.device)
+            elif tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"classifier_head_backward: gradient {i} must be a contiguous fp32 {shape} device tensor")
+            grads[i] = t
+        _timed(f"head_dparams<{name}>", dict(flops=2.0 * n * (w1.numel() + k * hid), bytes=float(4 * w1.numel() * (2 if accumulate else 1)), shape=f"N{n} F{s * c} H{hid} K{k}"),
+               lambda: check(lib().gm_head_dparams(h.data_ptr(), arena_ld(h), da.data_ptr(), a.data_ptr(), _ptr(mask), _ptr(g), _ptr(grads[0]), _ptr(grads[1]),
+                                                   _ptr(grads[2]), _ptr(grads[3]), n, s, c, hid, k, int(bool(accumulate)), dt_code(h.dtype), _stream()),
+                             "gm_head_dparams"))
+    return dh, tuple(grads)
+
+
 class VirtualCat:
     """Channel concatenation that is never materialised (reference: torch.cat([h, skip], dim=1), diffusion_model_unet.py:1232,
     1340,1461): its consumers read the parts directly."""

@@ -694,6 +694,30 @@ int gm_bn_bwd_apply(const void* x, long long x_ld, const void* gy, long long gy_
 int gm_patch_adv_loss(const void* x, long long total, int criterion, int act, float target, double out_scale, float* out, void* elem, const float* upstream,
                       const void* upstream_elem, void* dx, int dtype, void* stream);
 
+/* ---- The classifier head of DiffusionModelEncoder (networks/nets/diffusion_model_unet.py): Linear(F, H) -> ReLU -> Dropout -> Linear(H, K) ------------
+ * h is the arena (N, S, C) with h_ld elements between voxels, F = S * C <= 4096; W1 is (H, F) in the reference's flatten order, column f = c * S + s, and
+ * is read in place (16-byte loads along its rows, base 16-byte aligned): the activations are transposed through LDS instead.  dtype: the storage type of
+ * h, a, mask, g, logits, dh; wdtype: that of W1, b1, W2, b2 -- (GM_F32, GM_F32), (GM_BF16, GM_BF16) or (GM_BF16, GM_F32).  da and all parameter
+ * gradients are fp32.  Every sum is fp32 in a fixed order, no atomics.  H <= 4096, 1 <= K <= 1024.
+ * gm_head_chunk: samples a work-group holds in LDS (4 for GM_F32, 8 for GM_BF16; -1: unsupported); larger batches are looped over inside the entry points. */
+int gm_head_chunk(int dtype);
+/* a[n, j] = relu(b1[j] + sum_f W1[j, f] h[n, f]) * mask[n, j]   (mask: (N, H) or NULL; b1 may be NULL).  F a multiple of 4 (fp32 W1) or 8 (bf16 W1). */
+int gm_head_hidden(const void* h, long long h_ld, int N, int S, int C, const void* w1, const void* b1, const void* mask, void* a, int H, int dtype,
+                   int wdtype, void* stream);
+/* One launch, one work-group per sample.  Without g: logits[n, k] = b2[k] + sum_j W2[k, j] a[n, j] (stored when logits is given); with labels y (N):
+ * logp[n] = log_softmax(logits[n])[y[n]] and e = onehot(y[n]) - softmax(logits[n]), softmax in fp32.  With g (N, K) instead: e = g[n].
+ * da[n, j] = sum_k W2[k, j] e[k] (when da is given): the gradient of sum_n logp[n], or of a loss whose logit gradient is g, with respect to a. */
+int gm_head_tail(const void* a, const void* w2, const void* b2, const long long* y, const void* g, void* logits, float* logp, float* da, int N, int H, int K,
+                 int dtype, int wdtype, void* stream);
+/* dh[n, s, c] = sum_j dz[n, j] W1[j, c * S + s], dz = da * mask * [a > 0], in arena layout.  F a multiple of 32 (fp32 W1) or 64 (bf16 W1);
+ * min(N, chunk) * H + 32 * that multiple floats fit 64 KiB (H <= 1792 at a full bf16 chunk), else the call is refused naming H. */
+int gm_head_dinput(const float* da, const void* a, const void* mask, const void* w1, void* dh, long long dh_ld, int N, int S, int C, int H, int dtype, int wdtype,
+                   void* stream);
+/* dW1[j, c * S + s] = sum_n dz[n, j] h[n, s, c], db1[j] = sum_n dz[n, j] (need h, da), dW2[k, j] = sum_n g[n, k] a[n, j], db2[k] = sum_n g[n, k] (need g);
+ * any of the four may be NULL.  accumulate != 0 adds to what the outputs hold.  F a multiple of 4. */
+int gm_head_dparams(const void* h, long long h_ld, const float* da, const void* a, const void* mask, const void* g, float* dw1, float* db1, float* dw2,
+                    float* db2, int N, int S, int C, int H, int K, int accumulate, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
