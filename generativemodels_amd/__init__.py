@@ -27,7 +27,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 _MIRRORED = ["", ".networks", ".networks.nets", ".networks.nets.diffusion_model_unet", ".networks.nets.patchgan_discriminator", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",
-             ".inferers", ".utils", ".metrics", ".losses", ".losses.adversarial_loss"]
+             ".inferers", ".utils", ".metrics", ".losses", ".losses.adversarial_loss", ".losses.perceptual"]
 
 
 def install_as_generative(force: bool = False) -> None:

@@ -230,6 +230,13 @@ PROTOTYPES = {
     "gm_head_tail": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_head_dinput": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "gm_head_dparams": (C.c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + [C.c_int] * 7 + [c_vp]),
+    "gm_maxpool2d": (C.c_int, [c_vp, c_vp] + [C.c_int] * 6 + [c_vp]),
+    "gm_maxpool2d_bwd": (C.c_int, [c_vp, c_vp, c_vp] + [C.c_int] * 6 + [c_vp]),
+    "gm_lpips_layer_workspace_bytes": (c_ll, [C.c_int, c_ll, C.c_int, C.c_int]),
+    "gm_lpips_layer": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, C.c_int, c_ll, C.c_int, C.c_int, c_vp]),
+    "gm_lpips_layer_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_ll, C.c_int, C.c_int, c_vp]),
+    "gm_slice_gather": (C.c_int, [c_vp, c_vp, c_vp, c_ll] + [C.c_int] * 4 + [c_ll] * 5 + [c_vp, c_vp, C.c_int, C.c_int, c_vp]),
+    "gm_slice_gather_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_ll, c_ll] + [C.c_int] * 4 + [c_ll] * 5 + [c_vp, C.c_int, C.c_int, c_vp]),
 }
 
 _lib = None

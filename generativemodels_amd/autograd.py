@@ -30,6 +30,8 @@ Every function here works on arena tensors (N, *spatial, C) and runs native kern
                   from the coarsest up, each scale's gradient folded into the next finer scale's store
   classifier_head the DiffusionModelEncoder head Linear -> ReLU -> dropout mask -> Linear on the arena (gm_head_hidden + gm_head_tail); backward:
                   gm_head_tail (da from the logit gradient), gm_head_dinput, and gm_head_dparams only where a parameter asks for its gradient
+  max_pool2d / lpips_layer / slice_gather   the three kernels of PerceptualLoss beside the convolutions (csrc/perceptual.hip): pooling whose backward
+                  recomputes the arg-max, the per-tap LPIPS distance of two feature maps, the scaled slice images of a volume
   add / cat       residual add and channel concatenation
   to_arena / from_arena   the NC[D]HW <-> N[D]HWC permutations
 There is no eager fallback: a CPU tensor raises in the first native call."""
@@ -42,7 +44,7 @@ import torch
 
 from . import ops
 
-__all__ = ["classifier_head", "ssim_cs", "ms_ssim_factors", "cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
+__all__ = ["max_pool2d", "lpips_layer", "slice_gather", "classifier_head", "ssim_cs", "ms_ssim_factors", "cast", "scale", "leaky_relu", "kld", "batch_norm_act", "patch_adv_loss", "avg_pool", "norm_modulate_act","spade_modulate", "conv", "conv_transpose", "conv_dilated", "conv_transpose_dilated", "sigma_from_log_var", "linear", "group_norm_act", "layer_norm", "geglu", "resample2x", "resize", "embedding", "silu", "upsample_conv", "attention", "embed_tokens", "activation", "add", "cat", "to_arena", "from_arena"]
 
 
 def _tup(v, n):
@@ -1000,3 +1002,72 @@ def classifier_head(h: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor
     order of N C [D] H W, ReLU, an optional (N, H) multiplier (the dropout mask), Linear(H, K) -> logits (N, K).  Differentiable in h and the four
     parameters; the parameter-gradient kernel runs only where one of them requires grad."""
     return _ClassifierHead.apply(h, w1, b1, w2, b2, mask)
+
+
+class _MaxPool2d(torch.autograd.Function):
+    """MaxPool2d(kernel, 2) over an arena tensor; keeps its input only: the backward recomputes every window's arg-max (no index tensor)."""
+
+    @staticmethod
+    def forward(ctx, x, kernel):
+        ctx.save_for_backward(x)
+        ctx.kernel = kernel
+        return ops.max_pool2d(x, kernel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        return ops.max_pool2d_backward(x, gy.contiguous(), ctx.kernel), None
+
+
+def max_pool2d(x: torch.Tensor, kernel: int) -> torch.Tensor:
+    """MaxPool2d(kernel, stride 2) (kernel 2 or 3, floor mode, no padding) over an arena tensor (N, H, W, C), differentiable."""
+    return _MaxPool2d.apply(x, int(kernel))
+
+
+class _LpipsLayer(torch.autograd.Function):
+    """The LPIPS distance of one tap, fp32 [N], as a function of both feature maps; the channel weights are constants.  The backward recomputes the
+    norms from the features it reads anyway and writes only the gradients that are asked for."""
+
+    @staticmethod
+    def forward(ctx, f, g, w):
+        ctx.save_for_backward(f, g, w)
+        return ops.lpips_layer(f, g, w)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, up):
+        f, g, w = ctx.saved_tensors
+        df, dg = ops.lpips_layer_backward(f, g, w, up.to(torch.float32).contiguous(), need=(ctx.needs_input_grad[0], ctx.needs_input_grad[1]))
+        return df, dg, None
+
+
+def lpips_layer(f: torch.Tensor, g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """fp32 [N]: mean over pixels of sum_c w_c (f_c / (|f| + 1e-10) - g_c / (|g| + 1e-10))^2 over two arena feature maps, differentiable in both
+    (w: fp32 [C], not differentiated)."""
+    return _LpipsLayer.apply(f, g, w.detach())
+
+
+class _SliceGather(torch.autograd.Function):
+    """ops.slice_gather as a function of the volume (or image batch): the scaled three-channel arena images of the selected slices."""
+
+    @staticmethod
+    def forward(ctx, vol, axis, idx, shift, scale, dtype):
+        out, didx = ops.slice_gather(vol, axis, idx, shift, scale, dtype)
+        ctx.save_for_backward(scale, *(() if didx is None else (didx,)))
+        ctx.cfg = (tuple(vol.shape), axis, vol.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        scale, *didx = ctx.saved_tensors
+        shape, axis, dtype = ctx.cfg
+        return ops.slice_gather_backward(gout.contiguous(), shape, axis, didx[0] if didx else None, scale, dtype), None, None, None, None, None
+
+
+def slice_gather(vol: torch.Tensor, axis: Optional[int], idx: Optional[torch.Tensor], shift: torch.Tensor, scale: torch.Tensor,
+                 dtype: torch.dtype) -> torch.Tensor:
+    """(v - shift) / scale of the slices `idx` across `axis` of an (N, C, D, H, W) volume -- axis None: of an (N, C, H, W) batch -- as arena images
+    (M', P0, P1, 3) in `dtype`; differentiable in the volume."""
+    return _SliceGather.apply(vol, axis, idx, shift.detach(), scale.detach(), dtype)

@@ -3075,3 +3075,148 @@ def spectral_loss(x: torch.Tensor, y: torch.Tensor, plan: SpectralPlan, *, out_s
            lambda: check(lib().gm_spectral_loss(x.data_ptr(), y.data_ptr(), plan.batch, m[0], m[1], m[2], m[3], _ptr(upstream), _ptr(hx), _ptr(hy), _ptr(full),
                                                 _ptr(partials), _ptr(value), float(out_scale or 0.0), _stream()), "gm_spectral_loss"))
     return value, full, hx, hy
+
+
+# ---- PerceptualLoss (losses/perceptual.py): csrc/perceptual.hip -------------------------------------------------------------------------------------
+def max_pool2d(x: torch.Tensor, kernel: int) -> torch.Tensor:
+    """MaxPool2d(kernel, stride 2), kernel 2 or 3, floor mode, no padding, over an arena tensor (N, H, W, C)."""
+    require_device(x)
+    if x.dim() != 4:
+        raise ValueError("max_pool2d expects an arena tensor (N, H, W, C)")
+    x = x.contiguous()
+    n, h, w, c = x.shape
+    if kernel not in (2, 3) or h < kernel or w < kernel:
+        raise ValueError(f"max_pool2d: kernel 2 or 3 over an image at least as large, got kernel {kernel} over {h} x {w}")
+    y = torch.empty((n, (h - kernel) // 2 + 1, (w - kernel) // 2 + 1, c), dtype=x.dtype, device=x.device)
+    _timed(f"maxpool2d<{str(x.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float(x.element_size() * (x.numel() + y.numel())), shape=f"{tuple(x.shape)} k{kernel}"),
+           lambda: check(lib().gm_maxpool2d(x.data_ptr(), y.data_ptr(), n, h, w, c, kernel, dt_code(x.dtype), _stream()), "gm_maxpool2d"))
+    return y
+
+
+def max_pool2d_backward(x: torch.Tensor, gy: torch.Tensor, kernel: int) -> torch.Tensor:
+    """dx of max_pool2d from its input x and the output gradient gy: a gather that recomputes each window's arg-max (first maximum in row-major order)."""
+    require_device(x, gy)
+    x, gy = x.contiguous(), gy.contiguous()
+    n, h, w, c = x.shape
+    if tuple(gy.shape) != (n, (h - kernel) // 2 + 1, (w - kernel) // 2 + 1, c) or gy.dtype != x.dtype:
+        raise ValueError(f"max_pool2d_backward: gy {tuple(gy.shape)} {gy.dtype} is no output gradient of x {tuple(x.shape)} {x.dtype}")
+    dx = torch.empty_like(x)
+    _timed(f"maxpool2d_bwd<{str(x.dtype).split('.')[-1]}>", dict(flops=0.0, bytes=float(x.element_size() * (2 * x.numel() + gy.numel())), shape=f"{tuple(x.shape)} k{kernel}"),
+           lambda: check(lib().gm_maxpool2d_bwd(x.data_ptr(), gy.data_ptr(), dx.data_ptr(), n, h, w, c, kernel, dt_code(x.dtype), _stream()), "gm_maxpool2d_bwd"))
+    return dx
+
+
+LPIPS_CHANNELS = (64, 128, 192, 256, 384, 512)
+
+
+def _lpips_operands(f: torch.Tensor, g: torch.Tensor, w: torch.Tensor):
+    require_device(f, g, w)
+    if f.dim() < 3 or f.shape != g.shape or f.dtype != g.dtype:
+        raise ValueError(f"lpips_layer: two arena feature maps of one shape and dtype, got {tuple(f.shape)} {f.dtype} and {tuple(g.shape)} {g.dtype}")
+    c = f.shape[-1]
+    if c not in LPIPS_CHANNELS:
+        raise ValueError(f"lpips_layer: C = {c} is not one of {LPIPS_CHANNELS}, the tap widths of the AlexNet and VGG16 stacks")
+    if w.dtype != torch.float32 or w.numel() != c:
+        raise ValueError(f"lpips_layer: the channel weights are fp32 [{c}]")
+    return f.contiguous(), g.contiguous(), w.contiguous(), f.shape[0], math.prod(f.shape[1:-1]), c
+
+
+def lpips_layer(f: torch.Tensor, g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """fp32 [N]: per sample the mean over the pixels of sum_c w_c (f_c / (|f| + 1e-10) - g_c / (|g| + 1e-10))^2, |.| over a pixel's channels."""
+    f, g, w, n, hw, c = _lpips_operands(f, g, w)
+    out = torch.empty((n,), dtype=torch.float32, device=f.device)
+    nbytes = int(lib().gm_lpips_layer_workspace_bytes(n, hw, c, dt_code(f.dtype)))
+    if nbytes < 0:
+        raise ValueError(f"lpips_layer: geometry refused (N {n}, pixels {hw}, C {c})")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=f.device)
+    _timed(f"lpips_layer<{str(f.dtype).split('.')[-1]}>", dict(flops=float(10 * f.numel()), bytes=float(2 * f.element_size() * f.numel()), shape=str(tuple(f.shape))),
+           lambda: check(lib().gm_lpips_layer(f.data_ptr(), g.data_ptr(), w.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, n, hw, c, dt_code(f.dtype), _stream()),
+                         "gm_lpips_layer"))
+    return out
+
+
+def lpips_layer_backward(f: torch.Tensor, g: torch.Tensor, w: torch.Tensor, upstream: torch.Tensor, need=(True, True)):
+    """(df, dg) of sum_n upstream[n] * lpips_layer(f, g, w)[n] in the feature dtype, None where `need` does not ask; upstream fp32 [N].  A pixel whose feature
+    vector is all zero gets the gradient 0."""
+    f, g, w, n, hw, c = _lpips_operands(f, g, w)
+    require_device(upstream)
+    if upstream.dtype != torch.float32 or upstream.numel() != n:
+        raise ValueError(f"lpips_layer_backward: the upstream gradient is fp32 [{n}]")
+    if not (need[0] or need[1]):
+        return None, None
+    upstream = upstream.contiguous()
+    df, dg = torch.empty_like(f) if need[0] else None, torch.empty_like(g) if need[1] else None
+    _timed(f"lpips_layer_bwd<{str(f.dtype).split('.')[-1]}>",
+           dict(flops=float(14 * f.numel()), bytes=float((2 + int(need[0]) + int(need[1])) * f.element_size() * f.numel()), shape=str(tuple(f.shape))),
+           lambda: check(lib().gm_lpips_layer_bwd(f.data_ptr(), g.data_ptr(), w.data_ptr(), upstream.data_ptr(), _ptr(df), _ptr(dg), n, hw, c, dt_code(f.dtype),
+                                                  _stream()), "gm_lpips_layer_bwd"))
+    return df, dg
+
+
+SliceGeometry = namedtuple("SliceGeometry", "count extent channels p0 p1 s_n s_c s_a s_0 s_1")
+
+
+def slice_geometry(shape: Sequence[int], axis: Optional[int]) -> SliceGeometry:
+    """The slices across `axis` (2, 3 or 4) of a dense (N, C, D, H, W) volume as images over the two other spatial axes, in their order -- or, axis None, the
+    images of a dense (N, C, H, W) batch themselves: slice m = (n, s) = (m // extent, m % extent).  Strides in elements.  Pure host logic."""
+    shape = tuple(int(v) for v in shape)
+    if axis is None:
+        if len(shape) != 4:
+            raise ValueError("slice_geometry: a batch of images is (N, C, H, W)")
+        n, c, h, w = shape
+        return SliceGeometry(n, 1, c, h, w, c * h * w, h * w, 0, w, 1)
+    if len(shape) != 5 or axis not in (2, 3, 4):
+        raise ValueError("slice_geometry: a volume is (N, C, D, H, W) and its slices run across axis 2, 3 or 4")
+    stride = [math.prod(shape[i + 1:]) for i in range(5)]
+    keep = [a for a in (2, 3, 4) if a != axis]
+    return SliceGeometry(shape[0] * shape[axis], shape[axis], shape[1], shape[keep[0]], shape[keep[1]], stride[0], stride[1], stride[axis], stride[keep[0]],
+                         stride[keep[1]])
+
+
+def _slice_index(idx: Optional[torch.Tensor], geo: SliceGeometry, device):
+    """The selection on the device (int64), checked on the host first: unique slice numbers within the volume.  -> (device tensor or None, slices selected)."""
+    if idx is None:
+        return None, geo.count
+    if idx.is_cuda:
+        return idx, idx.numel()  # (already checked and uploaded: the backward hands the forward's tensor back)
+    idx = idx.to(torch.int64).contiguous()
+    if idx.dim() != 1 or idx.numel() < 1:
+        raise ValueError("slice_gather: the selection is a non-empty 1-D index tensor")
+    if int(idx.min()) < 0 or int(idx.max()) >= geo.count or torch.unique(idx).numel() != idx.numel():
+        raise ValueError(f"slice_gather: the selection must hold unique slice numbers in [0, {geo.count})")
+    return idx.to(device), idx.numel()
+
+
+def slice_gather(vol: torch.Tensor, axis: Optional[int], idx: Optional[torch.Tensor], shift: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype):
+    """The slices `idx` (host int64, unique; None: all, in order) across `axis` of a volume with 1 or 3 channels -- axis None: a batch of images -- as arena images
+    (M', P0, P1, 3) in `dtype`: (v - shift[c]) / scale[c], one channel broadcast to three.  -> (images, the selection on the device or None)."""
+    require_device(vol, shift, scale)
+    geo = slice_geometry(vol.shape, axis)
+    if geo.channels not in (1, 3):
+        raise ValueError(f"slice_gather: 1 or 3 channels, got {geo.channels}")
+    if shift.dtype != torch.float32 or scale.dtype != torch.float32 or shift.numel() != 3 or scale.numel() != 3:
+        raise ValueError("slice_gather: shift and scale are fp32 with three values")
+    vol, shift, scale = vol.contiguous(), shift.contiguous(), scale.contiguous()
+    didx, mp = _slice_index(idx, geo, vol.device)
+    out = torch.empty((mp, geo.p0, geo.p1, 3), dtype=dtype, device=vol.device)
+    _timed("slice_gather", dict(flops=0.0, bytes=float(out.numel() * (vol.element_size() + out.element_size())), shape=f"{tuple(vol.shape)} axis {axis} -> {tuple(out.shape)}"),
+           lambda: check(lib().gm_slice_gather(vol.data_ptr(), _ptr(didx), out.data_ptr(), mp, geo.extent, geo.channels, geo.p0, geo.p1, geo.s_n, geo.s_c, geo.s_a, geo.s_0,
+                                               geo.s_1, shift.data_ptr(), scale.data_ptr(), dt_code(vol.dtype), dt_code(dtype), _stream()), "gm_slice_gather"))
+    return out, didx
+
+
+def slice_gather_backward(gout: torch.Tensor, shape: Sequence[int], axis: Optional[int], didx: Optional[torch.Tensor], scale: torch.Tensor,
+                          dtype: torch.dtype) -> torch.Tensor:
+    """The volume gradient (`shape`, `dtype`) of slice_gather from the gradient of its images: zero outside the selected slices."""
+    require_device(gout, didx, scale)
+    geo = slice_geometry(shape, axis)
+    gout, scale = gout.contiguous(), scale.contiguous()
+    mp = geo.count if didx is None else didx.numel()
+    if tuple(gout.shape) != (mp, geo.p0, geo.p1, 3):
+        raise ValueError(f"slice_gather_backward: gradient {tuple(gout.shape)} for {mp} images of {geo.p0} x {geo.p1}")
+    dvol = torch.empty(tuple(shape), dtype=dtype, device=gout.device)
+    _timed("slice_gather_bwd", dict(flops=0.0, bytes=float(gout.numel() * gout.element_size() + dvol.numel() * dvol.element_size()), shape=f"{tuple(shape)} axis {axis}"),
+           lambda: check(lib().gm_slice_gather_bwd(gout.data_ptr(), _ptr(didx), dvol.data_ptr(), dvol.numel(), mp, geo.extent, geo.channels, geo.p0, geo.p1, geo.s_n,
+                                                   geo.s_c, geo.s_a, geo.s_0, geo.s_1, scale.data_ptr(), dt_code(gout.dtype), dt_code(dtype), _stream()),
+                         "gm_slice_gather_bwd"))
+    return dvol

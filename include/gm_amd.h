@@ -718,6 +718,30 @@ int gm_head_dinput(const float* da, const void* a, const void* mask, const void*
 int gm_head_dparams(const void* h, long long h_ld, const float* da, const void* a, const void* mask, const void* g, float* dw1, float* db1, float* dw2,
                     float* db2, int N, int S, int C, int H, int K, int accumulate, int dtype, void* stream);
 
+/* ---- PerceptualLoss (losses/perceptual.py): LPIPS over a frozen AlexNet / VGG16 stack; csrc/perceptual.hip ---------------------------------------------
+ * Dense channels-last arenas, fp32 or bf16; every sum in a fixed order, no atomics.
+ * gm_maxpool2d: y (N, Ho, Wo, C) = MaxPool2d(k, stride 2) of x (N, H, W, C), k = 2 or 3, floor mode (Ho = (H - k) / 2 + 1), no padding; a NaN wins its window.
+ * gm_maxpool2d_bwd: dx (N, H, W, C) from x and gy (N, Ho, Wo, C): every input element adds the gradient of each window whose arg-max it is -- the first
+ * maximum in row-major order inside the window, recomputed from x -- windows in row-major order, rounded to the dtype after each addition. */
+int gm_maxpool2d(const void* x, void* y, int N, int H, int W, int C, int k, int dtype, void* stream);
+int gm_maxpool2d_bwd(const void* x, const void* gy, void* dx, int N, int H, int W, int C, int k, int dtype, void* stream);
+/* out[n] (fp32) = mean over the HW pixels of sum_c w[c] (f_c / (|f| + 1e-10) - g_c / (|g| + 1e-10))^2 for features f, g (N, HW, C), |.| the norm over a pixel's
+ * channels; C is 64, 128, 192, 256, 384 or 512, w fp32 [C], every pointer 16-byte aligned.  workspace: gm_lpips_layer_workspace_bytes (-1: refused) of fp64
+ * work-group partials, folded in work-group order by a second launch.
+ * gm_lpips_layer_bwd: df and / or dg (either may be NULL; the dtype of f) = the gradient of sum_n up[n] out[n]; a pixel whose vector is all zero gets 0. */
+long long gm_lpips_layer_workspace_bytes(int N, long long HW, int C, int dtype);
+int gm_lpips_layer(const void* f, const void* g, const float* w, float* out, void* workspace, long long workspace_bytes, int N, long long HW, int C, int dtype,
+                   void* stream);
+int gm_lpips_layer_bwd(const void* f, const void* g, const float* w, const float* up, void* df, void* dg, int N, long long HW, int C, int dtype, void* stream);
+/* out (Mp, P0, P1, 3) = (v - shift[c]) / scale[c] over the slices idx[0 .. Mp) (device int64, unique; NULL: slices 0 .. Mp - 1 in order) of a volume with C = 1
+ * (broadcast) or 3 channels: slice m = (n, s) = (m / E, m % E), element (p0, p1) of channel c at vol[n sN + c sC + s sA + p0 s0 + p1 s1] (strides in elements).
+ * gm_slice_gather_bwd: dvol (vol_elems elements, zero-filled here when idx is given) at those slices = gout / scale, the three channels summed where C = 1.
+ * The two dtypes of each call: equal, or fp32 volumes with bf16 images. */
+int gm_slice_gather(const void* vol, const long long* idx, void* out, long long Mp, int E, int C, int P0, int P1, long long sN, long long sC, long long sA,
+                    long long s0, long long s1, const float* shift, const float* scale, int in_dtype, int out_dtype, void* stream);
+int gm_slice_gather_bwd(const void* gout, const long long* idx, void* dvol, long long vol_elems, long long Mp, int E, int C, int P0, int P1, long long sN,
+                        long long sC, long long sA, long long s0, long long s1, const float* scale, int g_dtype, int vol_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
