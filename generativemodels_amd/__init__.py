@@ -24,6 +24,8 @@ def __getattr__(name):
         from .graphs import GraphedForwardBackward
 
         return GraphedForwardBackward
+    if name == "optim":  # Adam / AdamW whose update is one native launch (optim.py)
+        return importlib.import_module(__name__ + ".optim")
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 _MIRRORED = ["", ".networks", ".networks.nets", ".networks.nets.diffusion_model_unet", ".networks.nets.patchgan_discriminator", ".networks.blocks", ".networks.blocks.spade_norm", ".networks.blocks.encoder_modules", ".networks.schedulers", ".networks.layers",

@@ -20,7 +20,7 @@ PUBLIC_HEADER = os.path.join(INCLUDE, "gm_amd.h")
 # "file.hip#k": the file compiled with -DGM_DMA_PART=k into its own object (conv_dma.hip: 26 kernel instantiations, 4.5 minutes as one
 # translation unit -- five parts build in parallel)
 SOURCES = ["capi.cpp", "elementwise.hip", "groupnorm.hip", "conv.hip", "conv_fast.hip", "conv_dma.hip#1", "conv_dma.hip#0", "conv_dma.hip#2", "conv_dma.hip#3",
-           "conv_dma.hip#4", "conv_sk.hip", "conv_sn.hip", "conv_edge.hip", "attention.hip", "attention_wide.hip", "attention_dma.hip", "attention_bwd.hip", "attention_bwd_dma.hip", "transformer_ops.hip", "decode_step.hip", "rows_gemm.hip", "decode_attention.hip", "backward.hip", "vq.hip", "metrics.hip", "metrics_bwd.hip", "spade_net.hip", "resize.hip", "spectral.hip", "batchnorm.hip", "adversarial_loss.hip", "classifier_head.hip", "perceptual.hip"]
+           "conv_dma.hip#4", "conv_sk.hip", "conv_sn.hip", "conv_edge.hip", "attention.hip", "attention_wide.hip", "attention_dma.hip", "attention_bwd.hip", "attention_bwd_dma.hip", "transformer_ops.hip", "decode_step.hip", "rows_gemm.hip", "decode_attention.hip", "backward.hip", "vq.hip", "metrics.hip", "metrics_bwd.hip", "spade_net.hip", "resize.hip", "spectral.hip", "batchnorm.hip", "adversarial_loss.hip", "classifier_head.hip", "perceptual.hip", "optim.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result", f"-I{INCLUDE}"]
 
@@ -60,7 +60,8 @@ def _stale(target: str, deps: list[str]) -> bool:
 
 # per-file extra flags: the scheduler / mixing kernels must reproduce the reference's fp32 op order bit for bit, so fused
 # multiply-add contraction is off for that translation unit (HIP's __fmul_rn/__fadd_rn are plain operators and DO contract)
-EXTRA_FLAGS = {"elementwise.hip": ["-ffp-contract=off"]}
+EXTRA_FLAGS = {"elementwise.hip": ["-ffp-contract=off"],
+               "optim.hip": ["-ffp-contract=off"]}  # (the 16-byte and the one-element path of the Adam update must give the same bits)
 
 
 # bench-only variants: extra defines, their own object directory and library name (the product library is never built with them).  The table

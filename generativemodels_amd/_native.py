@@ -237,6 +237,9 @@ PROTOTYPES = {
     "gm_lpips_layer_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_ll, C.c_int, C.c_int, c_vp]),
     "gm_slice_gather": (C.c_int, [c_vp, c_vp, c_vp, c_ll] + [C.c_int] * 4 + [c_ll] * 5 + [c_vp, c_vp, C.c_int, C.c_int, c_vp]),
     "gm_slice_gather_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_ll, c_ll] + [C.c_int] * 4 + [c_ll] * 5 + [c_vp, C.c_int, C.c_int, c_vp]),
+    "gm_adam_step": (C.c_int, [c_vp, c_ll, c_vp, c_vp, C.c_int, c_vp]),
+    "gm_adam_advance": (C.c_int, [c_vp, c_vp, C.c_int, c_vp]),
+    "gm_optim_upload": (C.c_int, [c_vp, c_vp, c_ll, c_vp]),
 }
 
 _lib = None

@@ -43,12 +43,17 @@ class GraphedForwardBackward:
              `reducer.no_sync()` and `reducer.finish()` after each step starts the exchange after the replay (a ring all-reduce of the 167 MB
              of C4 gradients is ~2 ms over xGMI, an eager backward costs 13 ms more than the replayed one).
     capture_exchange: None = whenever the reducer allows it (above), False = never.
+    optimizer: optional `generativemodels_amd.optim` optimizer (Adam / AdamW).  Its update is captured as the graph's last nodes, behind the backward and --
+             where the exchange is captured -- behind the exchange's join: a call is then a whole training step.  The warm-up steps do not step it.  Param
+             groups may change between calls (an LR scheduler): the changed rows of the device table are rewritten ahead of the replay.  With a reducer
+             whose exchange is NOT captured the update would run before the exchange: ValueError.  A torch optimizer is a TypeError (it steps after the
+             call, as before).
     warmup:  eager steps run before the capture (weight packing, kernel attribute set-up, allocator sizing, the reducer's first-step discovery
              of unused parameters).  They accumulate nothing: gradients are cleared before the capture.
     """
 
     def __init__(self, fn: Callable[..., torch.Tensor], example_inputs: Sequence[torch.Tensor], params: Iterable[torch.nn.Parameter],
-                 reducer=None, warmup: int = 2, capture_exchange: Optional[bool] = None) -> None:
+                 reducer=None, warmup: int = 2, capture_exchange: Optional[bool] = None, optimizer=None) -> None:
         self.fn = fn
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
@@ -60,6 +65,15 @@ class GraphedForwardBackward:
         red = self.reducer
         if capture_exchange and not (red is not None and getattr(red, "static_graph", False)):
             raise ValueError("GraphedForwardBackward(capture_exchange=True) needs an active GradientReducer(static_graph=True)")
+        self.optimizer = optimizer
+        if optimizer is not None:
+            from . import optim
+
+            if not isinstance(optimizer, optim.Adam):
+                raise TypeError(f"GraphedForwardBackward(optimizer=...) captures the update of a generativemodels_amd.optim optimizer, got {type(optimizer).__module__}."
+                                f"{type(optimizer).__name__}: a torch optimizer steps after the replay, outside the graph")
+            if red is not None and (capture_exchange is False or not getattr(red, "static_graph", False)):
+                raise ValueError(self._UNCAPTURED_EXCHANGE)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -68,6 +82,9 @@ class GraphedForwardBackward:
                 fn(*self.inputs).backward()
                 if red is not None:
                     red.finish()  # (a real exchange: the first one teaches the reducer which parameters ever receive a gradient)
+            if optimizer is not None:  # the warm-up moves neither the parameters nor the optimizer's state: no step, only what a capture cannot do
+                optimizer.ensure_state()  # (zero moments for the parameters the warm-up gave a gradient)
+                optimizer._warm()  # (the hyper-parameter rows; both kernels' first launch, on scratch tensors)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self._clear()
@@ -80,6 +97,8 @@ class GraphedForwardBackward:
             raise ValueError("GraphedForwardBackward(capture_exchange=True) needs GradientReducer(static_graph=True) on an RCCL (\"nccl\") group whose "
                              "warm-up steps recorded the gradient arrival order (warmup >= 2)")
         self.exchange_captured = bool(can and capture_exchange is not False)
+        if optimizer is not None and red is not None and not self.exchange_captured:
+            raise ValueError(self._UNCAPTURED_EXCHANGE)
         sync_off = red.no_sync() if (red is not None and not self.exchange_captured) else contextlib.nullcontext()
         # thread-local capture mode: HIP calls of other host threads (DataLoader pin-memory, the RCCL watchdog) do not invalidate the capture;
         # the autograd engine issues this backward's kernels on the capturing stream
@@ -93,10 +112,16 @@ class GraphedForwardBackward:
                 self.loss.backward()
             if self.exchange_captured:
                 red.finish()  # remaining launches, the waits, the join of the side stream, the division: stream work only in stage 2
+            if optimizer is not None:
+                optimizer.step()  # the graph's last nodes: behind the backward and, where the exchange is captured, behind its join
         # the gradient tensors the captured step writes: graph-pool allocations (or the reducer's bucket views); re-attached after every replay,
         # so an optimizer.zero_grad(set_to_none=True) between steps is harmless
         self.grads = [p.grad for p in self.params]
         self.loss = self.loss.detach()
+
+    _UNCAPTURED_EXCHANGE = ("GraphedForwardBackward(optimizer=...) with an active GradientReducer needs the exchange inside the graph "
+                            "(GradientReducer(static_graph=True) on an RCCL group, capture_exchange not False): the captured update would run before "
+                            "the gradients are exchanged")
 
     def _clear(self) -> None:
         if self.reducer is not None:
@@ -113,7 +138,11 @@ class GraphedForwardBackward:
             if dst.shape != src.shape or dst.dtype != src.dtype:
                 raise ValueError("GraphedForwardBackward: the captured step has fixed input shapes and dtypes")
             dst.copy_(src, non_blocking=True)
+        if self.optimizer is not None:
+            self.optimizer._sync_hyper()  # rows of the device table whose param group changed (an LR scheduler), ahead of the replay that reads them
         self.graph.replay()
+        if self.optimizer is not None:
+            self.optimizer._bump()  # the replay rewrote the parameters natively: their version counters key every derived cache
         for p, g in zip(self.params, self.grads):
             p.grad = g
         if self.exchange_captured:

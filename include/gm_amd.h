@@ -742,6 +742,21 @@ int gm_slice_gather(const void* vol, const long long* idx, void* out, long long 
 int gm_slice_gather_bwd(const void* gout, const long long* idx, void* dvol, long long vol_elems, long long Mp, int E, int C, int P0, int P1, long long sN,
                         long long sC, long long sA, long long s0, long long s1, const float* scale, int g_dtype, int vol_dtype, void* stream);
 
+/* ---- optim.Adam / AdamW (optim.py): the parameter update of every tensor in one launch; csrc/optim.hip ---------------------------------------------------
+ * table: n_entries x GM_OPTIM_ENTRY_WORDS 64-bit words in device memory, one entry per chunk of a tensor, one 256-thread work-group per entry:
+ *   [0..4] pointers to p, g (the dtype of the call), exp_avg, exp_avg_sq, max_exp_avg_sq (fp32; the last 0 without amsgrad)   [5] elements of the chunk
+ *   [6] index of the tensor's counter in steps   [7] bits 0..31: row of hyper, bit 32: every pointer is 16-byte aligned (16-byte accesses; else one element each,
+ *   same bits)
+ * hyper: rows of GM_OPTIM_HYPER_DOUBLES fp64: lr, beta1, beta2, eps, weight_decay, flags (1 amsgrad | 2 maximize | 4 decoupled weight decay), 0, 0.
+ * steps: fp32 counters; an entry is updated for t = steps[index] + 1 (bias corrections in fp64, once per work-group) and gm_adam_step writes no counter:
+ * gm_adam_advance, enqueued behind it, adds 1 to steps[active[i]], i < n_active (every index at most once).  No atomics.
+ * gm_optim_upload: an asynchronous copy of a table from page-locked host memory (a memcpy node when the stream is capturing). */
+#define GM_OPTIM_ENTRY_WORDS 8
+#define GM_OPTIM_HYPER_DOUBLES 8
+int gm_adam_step(const long long* table, long long n_entries, const float* steps, const double* hyper, int dtype, void* stream);
+int gm_adam_advance(float* steps, const int* active, int n_active, void* stream);
+int gm_optim_upload(void* dst, const void* src_pinned, long long bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
